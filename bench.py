@@ -2,7 +2,7 @@
 """Headline benchmark: cACGMM EM iterations/s on F=513, T=500, D=8, K=3
 (BASELINE.json metric / configs[1]), one rank per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path: one fused `fit` of --iters (default 100) EM iterations
 followed by the final E-step (fit_predict), with the complex64 observation already resident in
@@ -17,10 +17,20 @@ DHTV -> PSD -> gev+ban -> apply, the STRONG-scaling workload), `config4` (config
 + MVDR-Souden), `config5` (configs[4], joint GCACGMM), `f32` (packed-FP32 instantiation), the
 secondary single-utterance figures and the CPU baselines -- live in tools/bench_blocks.py.
 
+A plain run does only what the headline needs: set up, pre-heat and warm up, time the K steps,
+write the outputs of the last timed step when --dump-outputs is given, and print the line.
+Everything else -- the per-kernel roofline, the sustained-load figure, the oracle check, the CPU
+baseline, the packed-FP32 instantiation, configs[2..4], the secondary figures and the other
+--workload choices -- runs only with --full.
+
+--dump-outputs DIR: the posterior masks of the last timed step (what fit_predict hands its
+caller, all-gathered over the ranks at N > 1) as DIR/masks.npy, float64.  The inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+
 Output: the LAST line on stdout is one strict-JSON object of at most 8 KB (`compact_line`): the
-contract keys, `roofline`, `cpu_baseline`, `verify` and one-number summaries of every other
-workload.  The full blocks go to `bench_extra.json` (in gpurun_out/ when that directory exists,
-else the working directory; `--extra-file` overrides).
+contract keys and, with --full, `roofline`, `cpu_baseline`, `verify` and one-number summaries of
+every other workload.  With --full the full blocks also go to `bench_extra.json` (`--extra-file`
+says where).
 """
 import argparse
 import json
@@ -101,7 +111,17 @@ def parse():
     p.add_argument('--print-source-sha', action='store_true',
                    help='print the hash of the kernel sources of --workload (tools/profile_round.sh '
                         'stamps it into the profile summaries) and exit')
-    return p.parse_args()
+    p.add_argument('--full', action='store_true',
+                   help='also run everything beyond the headline: roofline, sustained load, oracle '
+                        'check, CPU baseline, f32, configs[2..4], secondary figures, the other '
+                        '--workload choices; the options above that switch those parts apply '
+                        'only with --full')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the outputs of the last timed step to DIR/<name>.npy')
+    args = p.parse_args()
+    if args.workload != 'config2' and not (args.full or args.print_source_sha):
+        p.error(f'--workload {args.workload} is one of the --full measurements')
+    return args
 
 
 # ------------------------------------------------------------------------------------------
@@ -201,6 +221,25 @@ def timed(step, steps, warmup, use_dist, dev, read_ms=None):
     return elapsed, kernel_ms / max(steps, 1), last
 
 
+DUMP_LIMIT = 64 << 20     # bytes of --dump-outputs in all
+
+
+def dump_outputs(directory, arrays):
+    """{name: host array} -> directory/<name>.npy as float64 (float32 stays float32).  An array
+    that would push the total past DUMP_LIMIT is replaced by a fixed, seeded sample of its
+    flattened elements (the same indices on every run)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    budget = DUMP_LIMIT // max(len(arrays), 1) - 4096   # room for the .npy header
+    for name, a in arrays.items():
+        if a.nbytes > budget:
+            n = budget // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + '.npy'), a)
+
+
 def sustained(step, seconds, ms_per_step, min_steps, use_dist, dev, read_ms=None):
     """The same step back to back for >= `seconds` after the timed region (DVFS give-back)."""
     if seconds <= 0:
@@ -256,7 +295,10 @@ def roofline_block(kernel_ms, bins, iters, ms_per_step=None, world_note='', peak
 # ------------------------------------------------------------------------------------------
 # headline: BASELINE configs[1]
 # ------------------------------------------------------------------------------------------
-def run_headline(args, world, rank, local_rank, dev, use_dist, precision='f64'):
+def run_headline(args, world, rank, local_rank, dev, use_dist, precision='f64', full=True):
+    """-> (line dict, (Y, init) of utterance 0, masks of the last timed step on the device) on
+    rank 0, None elsewhere.  full=False: the headline alone -- no kernel events, no sustained
+    run, no exchange timing, no oracle check."""
     import torch
     import bench_blocks as bb
     from pb_bss_amd.testing import synth  # input generator shared with the parity tests
@@ -269,7 +311,8 @@ def run_headline(args, world, rank, local_rank, dev, use_dist, precision='f64'):
     y = _lib.to_device(np.concatenate([d[0][lo:hi] for d in data]))   # (world*(hi-lo), T, D) c64
     g0 = _lib.to_device(np.concatenate([d[1][lo:hi] for d in data]))  # (world*(hi-lo), K, T) f64
     n_loc = hi - lo
-    engine.set_timing(True, local_rank)
+    if full:
+        engine.set_timing(True, local_rank)
     fit_kw = {} if precision == 'f64' else {'precision': 'f32'}
 
     def step():
@@ -285,17 +328,18 @@ def run_headline(args, world, rank, local_rank, dev, use_dist, precision='f64'):
 
     # HIP events on the dispatch of the EM kernel (library, launch stream), read TWO launches late:
     # reading the most recent launch would drain the queue every step
-    read_ms = lambda lag: engine.last_kernel_ms(local_rank, lag)  # noqa: E731
+    read_ms = (lambda lag: engine.last_kernel_ms(local_rank, lag)) if full else None
     ph = preheat(step, args.preheat_s, use_dist, dev)
     elapsed, kernel_ms, last = timed(step, args.steps, args.warmup, use_dist, dev, read_ms)
     ms_per_step = elapsed / args.steps * 1e3
-    sus = sustained(step, args.sustained_s, ms_per_step, args.steps, use_dist, dev, read_ms)
+    sus = sustained(step, args.sustained_s, ms_per_step, args.steps, use_dist, dev, read_ms) \
+        if full else None
     masks, r = last['masks'], last['r']
 
     # ---- the exchange step on its own (untimed region): HIP events around the gather ----
     gather_ms = None
     mine = {'em_kernel_ms': kernel_ms, 'bins_per_utterance': float(n_loc)}
-    if use_dist:
+    if use_dist and full:
         loc = r['affiliation'].reshape(world, n_loc, K, T)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         fence(use_dist)
@@ -306,10 +350,11 @@ def run_headline(args, world, rank, local_rank, dev, use_dist, precision='f64'):
         torch.cuda.synchronize()
         mine['gather_ms'] = e0.elapsed_time(e1) / 10
         gather_ms = max_over_ranks(mine['gather_ms'], use_dist, dev)
-    same = bb.identical_on_all_ranks(masks, use_dist, world)
-    per_rank = bb.per_rank_table(mine, use_dist, world, dev)
+    if full:
+        same = bb.identical_on_all_ranks(masks, use_dist, world)
+        per_rank = bb.per_rank_table(mine, use_dist, world, dev)
     got2 = None
-    if precision != 'f64' and args.check_bins:
+    if full and precision != 'f64' and args.check_bins:
         # per-step check of the single-precision kernel (see the verification below): two
         # iterations from the same initialisation, a separate untimed launch on every rank
         r2 = engine.em_fit(y, K, gamma0=g0, iterations=2, final_predict=True, check_status=False,
@@ -355,11 +400,14 @@ def run_headline(args, world, rank, local_rank, dev, use_dist, precision='f64'):
         },
         'status_bits_or': status_or,
         'preheat': ph,
-        'sustained': sus,
-        'per_rank': dict(per_rank, what='per rank: EM kernel ms per step (HIP events in the library, '
-                                        'average over the timed steps), its bins per utterance, '
-                                        'and -- N > 1 -- its time for one mask all-gather'),
     }
+    if not full:
+        return out, data[0], masks
+    out['sustained'] = sus
+    out['per_rank'] = dict(per_rank, what='per rank: EM kernel ms per step (HIP events in the '
+                                          'library, average over the timed steps), its bins per '
+                                          'utterance, and -- N > 1 -- its time for one mask '
+                                          'all-gather')
     if precision == 'f64':
         out['roofline'] = roofline_block(kernel_ms, world * n_loc, args.iters, ms_per_step)
     else:
@@ -376,7 +424,7 @@ def run_headline(args, world, rank, local_rank, dev, use_dist, precision='f64'):
     # ---- parity: bins of EVERY rank's shard of EVERY utterance (oracle = checker only) ----
     if args.check_bins:
         bb.verify_headline(out, args, world, data, _lib.to_host(masks), got2, same, precision)
-    return out, data[0]
+    return out, data[0], masks
 
 
 # ------------------------------------------------------------------------------------------
@@ -507,7 +555,7 @@ def emit(full, use_dist, args=None):
         dist.destroy_process_group()
     if full is None:
         return
-    path = write_extra(full, extra_path_for(args) if args is not None else None)
+    path = write_extra(full, extra_path_for(args)) if args is not None and args.full else None
     line = compact_line(full, path)
     # RCCL writes a version banner through C stdio; when stdout is a pipe it sits in libc's buffer
     # until exit and would land AFTER the JSON line: flush it out first
@@ -535,10 +583,17 @@ def main():
     if args.workload in ('config4', 'config5'):
         return bb.main_config45(args)
     world, rank, local_rank, dev, use_dist = setup(args)
-    res = run_headline(args, world, rank, local_rank, dev, use_dist)
+    res = run_headline(args, world, rank, local_rank, dev, use_dist, full=args.full)
     out = None
     if rank == 0:
-        out, (Y0, init0) = res
+        out, (Y0, init0), masks = res
+        if args.dump_outputs:
+            from pb_bss_amd import _lib
+            dump_outputs(args.dump_outputs, {'masks': _lib.to_host(masks)})
+    if not args.full:
+        emit(out, use_dist, args)
+        return
+    if rank == 0:
         # ---- CPU baseline on this host, bounded sample (rank 0, N = 1 only) ----
         if world == 1 and args.cpu_iters > 0:
             out['cpu_baseline'] = bb.cpu_baseline_em(Y0, init0, args.cpu_iters)
@@ -566,7 +621,7 @@ def main():
             if isinstance(r32, dict):
                 out['f32'] = r32
             else:
-                f32, _ = r32
+                f32 = r32[0]
                 out['f32'] = {k: f32[k] for k in ('value', 'unit', 'ms_per_step', 'dtype',
                                                   'config', 'roofline', 'status_bits_or',
                                                   'sustained', 'verify') if k in f32}

@@ -620,6 +620,110 @@ def public_names_cases():
           mixw_outer=mmu.estimate_mixture_weight(aff, weight_constant_axis=(0, -1)))
 
 
+def reference_live_cases():
+    """The unmodified reference on the inputs of tests/test_reference_live.py (the committed
+    fixtures it re-derives and the seeded draws it compares the oracle with) ->
+    tests/golden/reference_live.npz.  The test rebuilds the same inputs from the same seeds."""
+    import pb_bss.distribution as dist
+    import pb_bss.extraction.beamformer as bf
+    import pb_bss.permutation_alignment as pa
+    out = {}
+    # the committed fixtures, re-derived
+    g = np.load(os.path.join(OUT, 'cacgmm_f9_t120_d8_k3.npz'))
+    model = dist.CACGMMTrainer().fit(g['Y'].astype(np.complex128), initialization=g['init'],
+                                     iterations=int(g['iterations']))
+    out['fixture_cacgmm_affiliation'] = model.predict(g['Y'].astype(np.complex128))
+    g = np.load(os.path.join(OUT, 'beamformer_extra_f19_d5.npz'))
+    out['fixture_lcmv_10'] = bf.get_lcmv_vector(g['atf'], [1, 0], g['noise'])
+    out['fixture_phase_3d'] = bf.phase_correction(g['wb'])
+    # fresh draws: CACGMM, GCACGMM, PSD, MVDR-Souden, the permutation solvers
+    Y, e, init = synth.make_joint(7, 90, 5, 2, 8, seed=1234)
+    Y128, e64 = Y.astype(np.complex128), e.astype(np.float64)
+    m = dist.CACGMMTrainer().fit(Y128, initialization=init, iterations=6)
+    masks = m.predict(Y128)
+    out['cacgmm_masks'] = masks
+    mj = dist.GCACGMMTrainer().fit(Y128, e64, initialization=init, iterations=4)
+    out['gcacgmm_masks'] = mj.predict(Y128, e64)
+    X = Y128.transpose(0, 2, 1)
+    psd = bf.get_power_spectral_density_matrix(X, masks)
+    out['psd'] = psd
+    out['mvdr_souden'] = bf.get_mvdr_vector_souden(psd[:, 0], psd[:, 1], ref_channel=0)
+    solver = pa.DHTVPermutationAlignment(stft_size=12, segment_start=2, segment_width=3,
+                                         segment_shift=1, main_iterations=5, sub_iterations=2)
+    kft = np.ascontiguousarray(masks.transpose(1, 0, 2))
+    out['dhtv_plan'] = np.asarray(solver.alignment_plan)
+    out['dhtv_mapping'] = solver.calculate_mapping(kft)
+    for metric in ('cos', 'multiply', 'euclidean'):
+        out[f'greedy_{metric}'] = \
+            pa.GreedyPermutationAlignment(similarity_metric=metric).calculate_mapping(kft)
+        shuffled = np.ascontiguousarray(kft[::-1])
+        for alg in ('greedy', 'optimal'):
+            out[f'oracle_{metric}_{alg}'] = \
+                pa.OraclePermutationAlignment(metric, alg).calculate_mapping(shuffled, kft)
+    # fresh draws: GMM and the Gaussian single fits
+    rng = np.random.default_rng(4321)
+    N, E, K = 700, 9, 3
+    centers = rng.normal(size=(K, E)) * 2
+    y = centers[rng.integers(K, size=N)] + rng.normal(size=(N, E))
+    init = rng.uniform(size=(K, N))
+    init /= init.sum(0, keepdims=True)
+    sal = rng.uniform(0.2, 1.0, size=N)
+    for ct in ('full', 'spherical'):
+        m = dist.GMMTrainer().fit(y, initialization=init, iterations=5, saliency=sal,
+                                  covariance_type=ct)
+        out[f'gmm_{ct}_mean'] = m.gaussian.mean
+        out[f'gmm_{ct}_covariance'] = m.gaussian.covariance
+        out[f'gmm_{ct}_weight'] = m.weight
+        out[f'gmm_{ct}_predict'] = m.predict(y)
+    w = rng.uniform(size=(K, N))
+    g = dist.GaussianTrainer()._fit(y[None], saliency=w, covariance_type='full')
+    out['gaussian_mean'] = g.mean
+    out['gaussian_covariance'] = g.covariance
+    out['gaussian_log_pdf'] = g.log_pdf(y[None])
+    # fresh draws: mixture-weight axes of VMFMM / GMM, diagonal covariances
+    rng = np.random.default_rng(11)
+    y = rng.standard_normal((3, 120, 5)) + rng.integers(0, 3, size=(3, 120, 1)) * 2.0
+    init = rng.uniform(size=(3, 3, 120))
+    init /= init.sum(axis=1, keepdims=True)
+    sal = rng.uniform(0.2, 1.0, size=(3, 120))
+    for i, axis in enumerate(((-3,), (-3, -1))):
+        m = dist.VMFMMTrainer().fit(y, initialization=init, iterations=3, saliency=sal,
+                                    weight_constant_axis=axis)
+        out[f'axes{i}_vmfmm_weight'] = m.weight
+        out[f'axes{i}_vmfmm_mean'] = m.vmf.mean
+        g = dist.GMMTrainer().fit(y, initialization=init, iterations=3, saliency=sal,
+                                  weight_constant_axis=axis, covariance_type='full')
+        out[f'axes{i}_gmm_weight'] = g.weight
+        out[f'axes{i}_gmm_covariance'] = g.gaussian.covariance
+    for i, axis in enumerate(((-1,), (-2,), -2)):
+        g = dist.GMMTrainer().fit(y[0], initialization=init[0], iterations=3, saliency=sal[0],
+                                  weight_constant_axis=axis, covariance_type='diagonal')
+        out[f'diag{i}_mean'] = g.gaussian.mean
+        out[f'diag{i}_covariance'] = g.gaussian.covariance
+        out[f'diag{i}_predict'] = g.predict(y[0])
+    _save('reference_live', **out)
+
+
+def reference_live_gev_cases():
+    """The reference's two Cython modules on the inputs of
+    tests/test_reference_live.py::test_gev_use_eig_fixture_equals_reference_cython_modules ->
+    tests/golden/reference_live_gev.npz (the test rebuilds the same pencils from the same seed)."""
+    import pb_bss.extraction.beamformer as bf
+    assert bf.c_eig_available and bf.c_gev_available, 'build the .pyx first (refshim.load_cython)'
+    g = np.load(os.path.join(OUT, 'gev_use_eig.npz'))
+    out = {}
+    for tag in ('hpd_d6', 'indef_d5', 'general_d6'):
+        out[tag + '_w'] = bf.get_gev_vector(g[tag + '_target'], g[tag + '_noise'], use_eig=True)
+    rng = np.random.default_rng(99)
+    A = rng.standard_normal((6, 5, 5)) + 1j * rng.standard_normal((6, 5, 5))
+    B = rng.standard_normal((6, 5, 5)) + 1j * rng.standard_normal((6, 5, 5)) + 2 * np.eye(5)
+    out['general_w_eig'] = bf.get_gev_vector(A, B, use_eig=True)     # c_eig.pyx (zggev)
+    X = rng.standard_normal((6, 5, 20)) + 1j * rng.standard_normal((6, 5, 20))
+    P = X @ X.conj().swapaxes(-1, -2)
+    out['hpd_w_zhegvd'] = bf.get_gev_vector(P, P + np.eye(5))         # get_gev_vector.pyx
+    _save('reference_live_gev', **out)
+
+
 def main():
     """python -m oracle.make_golden            -> every fixture of the pure-Python reference
     python -m oracle.make_golden f32k56     -> tests/golden/cacgmm_single_precision_k56.npz
@@ -629,7 +733,10 @@ def main():
     python -m oracle.make_golden public_names -> tests/golden/public_names_r06.npz
     python -m oracle.make_golden gev_eig    -> tests/golden/gev_use_eig.npz only (own process:
     the reference's Cython modules must be injected BEFORE pb_bss.extraction.beamformer is
-    imported, and the other fixtures are defined as the Cython-less reference's output)."""
+    imported, and the other fixtures are defined as the Cython-less reference's output)
+    python -m oracle.make_golden live       -> tests/golden/reference_live.npz
+    python -m oracle.make_golden live_gev   -> tests/golden/reference_live_gev.npz (own process,
+    as gev_eig)."""
     import sys
     os.makedirs(OUT, exist_ok=True)
     warnings.filterwarnings('ignore', category=DeprecationWarning)
@@ -656,6 +763,14 @@ def main():
     if sys.argv[1:] == ['gev_eig']:
         refshim.load_cython()
         gev_eig_cases()
+        return
+    if sys.argv[1:] == ['live']:
+        refshim.load()
+        reference_live_cases()
+        return
+    if sys.argv[1:] == ['live_gev']:
+        refshim.load_cython()
+        reference_live_gev_cases()
         return
     refshim.load()
     cacgmm_cases()

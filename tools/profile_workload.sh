@@ -19,7 +19,7 @@ WARM=3
 [ "$WL" = config3 ] && STEPS=6 && WARM=2
 NAME=$WL
 [ "$WL" = config4 ] && [ "$LEG" = vmf ] && NAME=config4_vmf
-CMD="python $ROOT/bench.py --workload $WL --leg $LEG --steps $STEPS --warmup $WARM --cpu-iters 0 --check-bins 0 --c4-extraction off --preheat-s 0.3"
+CMD="python $ROOT/bench.py --full --workload $WL --leg $LEG --steps $STEPS --warmup $WARM --cpu-iters 0 --check-bins 0 --c4-extraction off --preheat-s 0.3"
 D="$OUT/prof_${TAG}_$NAME"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp

@@ -8,6 +8,7 @@ MARK=cwmm_em_wide_kernel; [ "$LEG" = vmf ] && MARK=vmf_bin_em2_kernel
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_chain_$LEG
 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/prof_chain_$LEG -o p -- python $R/bench.py --workload config4 \
+  --full \
   --leg $LEG --steps 10 --warmup 3 --cpu-iters 0 --check-bins 0 --preheat-s 0.2 --extra-file none > $R/gpurun_out/chain_$LEG.log 2>&1
 cd $R
 python - "$LEG" "$MARK" <<'PY' | tee gpurun_out/chain_step_$LEG.txt
