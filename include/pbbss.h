@@ -31,7 +31,9 @@
 extern "C" {
 #endif
 
-#define PBBSS_VERSION 610 /* 0.6.1: pbbss_select_reference_channel, pbbss_apply_beamforming_vector_shared;
+#define PBBSS_VERSION 610 /* still 0.6.1 (the value is pinned by the symbol test): pbbss_cbmm_fit,
+                             pbbss_cbingham_find_eigenvalues, PBBSS_ST_SOLVE_NOCONV added since;
+                             0.6.1: pbbss_select_reference_channel, pbbss_apply_beamforming_vector_shared;
                              0.6.0: pbbss_log_pdf_to_affiliation_inline_pa, D = 33 / 34 in pbbss_cacgmm_fit / _predict;
                              0.4.1: pbbss_set_dhtv_probe; 0.4.0: pbbss_split_reset, pbbss_set_spin_limit, pbbss_reference_channel_terms,
                              pbbss_rank_one_approximation, pbbss_matvec (0.3.0: em_opts.precision,
@@ -53,6 +55,7 @@ extern "C" {
 #define PBBSS_ST_SLOWPATH 8u       /* in-loop eigen path was taken (informational) */
 #define PBBSS_ST_NOT_POSDEF 16u    /* Cholesky of B failed (GEV: LAPACK INFO > N)  */
 #define PBBSS_ST_SINGULAR 32u      /* LU met a zero pivot (np.linalg.LinAlgError)  */
+#define PBBSS_ST_SOLVE_NOCONV 64u  /* complex Bingham parameter solve did not converge */
 
 typedef struct pbbss_handle_s* pbbss_handle_t;
 
@@ -463,6 +466,55 @@ int pbbss_cwmm_fit(pbbss_handle_t h, const void* y, int64_t B, int T, int D, int
                    double* out_concentration, double* out_weight,
                    int32_t* out_status, double* out_affiliation,
                    double* out_log_pdf, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* N2  CBMMTrainer.fit / fit_predict, CBMM.predict   distribution/cbmm.py:21-237; */
+/*     ComplexBingham.log_pdf / norm / _remove_duplicate_eigenvalues              */
+/*     complex_bingham.py:60-224; ComplexBinghamTrainer.find_eigenvalues_v3 /     */
+/*     _fit  :304-396, :571-594.                                                  */
+/* y (B,T,D) complex, raw (the kernel unit-normalises, complex_bingham.py:12-25). */
+/* Initialisation: gamma0 (B,K,T) f64 affiliations, or a model (in_eigvec c128   */
+/* (B,K,D,D) eigenvectors in columns, in_eigval f64 (B,K,D) Bingham eigenvalues,  */
+/* in_weight f64 (B,K)).  iterations may be 0 with a model (pure predict).        */
+/* The Bingham parameters are solved in-kernel (csrc/cbmm.hpp): the normaliser as */
+/* a divided difference of exp by scaling and squaring, the D-1 consecutive       */
+/* differences of lam by bounded Gauss-Newton to rounding level.  saliency f64    */
+/* (B,T) or NULL.  weight_mode: PBBSS_WEIGHT_PER_CLASS_MEAN or _UNIFORM.          */
+/* Outputs: eigvec c128 (B,K,D,D) (numpy.linalg.eigh order), eigval f64 (B,K,D),  */
+/* ln c f64 (B,K) (may be NULL), weight f64 (B,K), status int32 (B,K):            */
+/* PBBSS_ST_SOLVE_NOCONV, PBBSS_ST_NONFINITE (also a negative scatter eigenvalue, */
+/* complex_bingham.py:589), PBBSS_ST_EIG_NOCONV; optional affiliation / log_pdf   */
+/* f64 (B,K,T) of the final E-step (final_predict).  2 <= D <= 8, 1 <= K <= 4,     */
+/* else PBBSS_ERR_UNSUPPORTED.  Frames LDS-resident, or in a per-workgroup HBM   */
+/* scratch slab when they do not fit (long utterances).  With a model and        */
+/* iterations = 0, out_lognorm receives ln c of the given eigenvalues.            */
+/* ------------------------------------------------------------------------- */
+typedef struct pbbss_cbmm_opts {
+  int32_t iterations;
+  int32_t weight_mode;        /* PBBSS_WEIGHT_PER_CLASS_MEAN / PBBSS_WEIGHT_UNIFORM */
+  int32_t y_is_c128;
+  int32_t final_predict;
+  double max_concentration;   /* > 0; +inf: no bound (the reference's default)   */
+  double eigenvalue_eps;      /* >= 0; the reference's default 1e-8               */
+  double norm_eps;            /* >= 0; de-duplication spacing of ln c (ComplexBingham.norm's eps,
+                               * 1e-8 in every log_pdf of the reference; 0: no de-duplication) */
+} pbbss_cbmm_opts;
+
+int pbbss_cbmm_fit(pbbss_handle_t h, const void* y, int64_t B, int T, int D, int K,
+                   const double* gamma0, const void* in_eigvec, const double* in_eigval,
+                   const double* in_weight, const double* saliency, const pbbss_cbmm_opts* opts,
+                   void* out_eigvec, double* out_eigval, double* out_lognorm,
+                   double* out_weight, int32_t* out_status, double* out_affiliation,
+                   double* out_log_pdf, void* stream);
+
+/* ComplexBinghamTrainer.find_eigenvalues_v3   complex_bingham.py:304-396.        */
+/* scatter_eigenvalues f64 (N,D), any order -> out_eigenvalues f64 (N,D) in the   */
+/* same order, out_status int32 (N) as above.  Same solver as pbbss_cbmm_fit.     */
+/* 2 <= D <= 8, else PBBSS_ERR_UNSUPPORTED.                                       */
+int pbbss_cbingham_find_eigenvalues(pbbss_handle_t h, const double* scatter_eigenvalues,
+                                    int64_t N, int D, double eigenvalue_eps,
+                                    double max_concentration, double* out_eigenvalues,
+                                    int32_t* out_status, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* N2/N3  Real-embedding mixture components: von Mises-Fisher and spherical      */

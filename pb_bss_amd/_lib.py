@@ -27,6 +27,7 @@ ST_FLOORED = 4
 ST_SLOWPATH = 8
 ST_NOT_POSDEF = 16
 ST_SINGULAR = 32
+ST_SOLVE_NOCONV = 64  # complex Bingham parameter solve did not converge
 
 COVNORM = {False: 0, None: 0, 'eigenvalue': 1, 'trace': 2}
 WEIGHT_PER_CLASS_MEAN = 0
@@ -50,6 +51,7 @@ EXPORTS = (
     'pbbss_select_reference_channel', 'pbbss_set_timing',
     'pbbss_last_kernel_ms', 'pbbss_kernel_ms_lagged', 'pbbss_set_phase_profile',
     'pbbss_dhtv_calculate_mapping', 'pbbss_apply_mapping', 'pbbss_cwmm_fit',
+    'pbbss_cbmm_fit', 'pbbss_cbingham_find_eigenvalues',
     'pbbss_wmwf', 'pbbss_set_split_tail', 'pbbss_split_error', 'pbbss_split_reset', 'pbbss_set_spin_limit',
     'pbbss_embed_log_pdf', 'pbbss_embed_fit', 'pbbss_vmfmm_fit', 'pbbss_joint_fit',
     'pbbss_lcmv', 'pbbss_phase_correction', 'pbbss_snr_postfilter',
@@ -103,6 +105,19 @@ class CwmmOpts(ctypes.Structure):
         ('ev_min', ctypes.c_double),
         ('ev_max', ctypes.c_double),
         ('max_concentration', ctypes.c_double),
+    ]
+
+
+class CbmmOpts(ctypes.Structure):
+    """struct pbbss_cbmm_opts"""
+    _fields_ = [
+        ('iterations', ctypes.c_int32),
+        ('weight_mode', ctypes.c_int32),
+        ('y_is_c128', ctypes.c_int32),
+        ('final_predict', ctypes.c_int32),
+        ('max_concentration', ctypes.c_double),
+        ('eigenvalue_eps', ctypes.c_double),
+        ('norm_eps', ctypes.c_double),
     ]
 
 
@@ -243,6 +258,9 @@ def load():
         lib.pbbss_zero_degree_normalization.argtypes = [vp, vp, i64, i32, i32, vp, vp]
         lib.pbbss_condition_covariance.argtypes = [vp, vp, i64, i32, dbl, vp, vp]
         lib.pbbss_apply_online_beamforming_vector.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp]
+        lib.pbbss_cbmm_fit.argtypes = ([vp, vp, i64, i32, i32, i32] + [vp] * 5 +
+                                       [ctypes.POINTER(CbmmOpts)] + [vp] * 8)
+        lib.pbbss_cbingham_find_eigenvalues.argtypes = [vp, vp, i64, i32, dbl, dbl, vp, vp, vp]
         for name in EXPORTS:
             fn = getattr(lib, name)
             if name not in ('pbbss_error_string',):

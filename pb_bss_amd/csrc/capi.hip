@@ -12,6 +12,7 @@
 #include "generic_bf.hpp"
 #include "stft.hpp"
 #include "em_launch.hpp"
+#include "cbmm_launch.hpp"
 #include "comm.hpp"
 
 #define PBBSS_API extern "C" __attribute__((visibility("default")))
@@ -1332,6 +1333,69 @@ PBBSS_API int pbbss_cwmm_fit(pbbss_handle_t h, const void* y, int64_t B, int T, 
   wa.out_conc = out_concentration;
   TimedRegion tr(h, as_stream(stream));
   return pbbss::cw_launch(D, K, o->y_is_c128, wa, h->cfg, as_stream(stream));
+}
+
+PBBSS_API int pbbss_cbmm_fit(pbbss_handle_t h, const void* y, int64_t B, int T, int D, int K,
+                             const double* gamma0, const void* in_eigvec, const double* in_eigval,
+                             const double* in_weight, const double* saliency,
+                             const pbbss_cbmm_opts* o, void* out_eigvec, double* out_eigval,
+                             double* out_lognorm, double* out_weight, int32_t* out_status,
+                             double* out_affiliation, double* out_log_pdf, void* stream) {
+  DeviceGuard device_guard(h);
+  if (!h || !y || !o || B <= 0 || T <= 0) return PBBSS_ERR_INVALID_ARG;
+  if (o->iterations < 0) return PBBSS_ERR_INVALID_ARG;
+  const bool has_gamma = gamma0 != nullptr;
+  const bool has_model = in_eigvec && in_eigval && in_weight;
+  if (has_gamma == has_model) return PBBSS_ERR_INVALID_ARG;
+  if (o->iterations == 0 && !has_model) return PBBSS_ERR_INVALID_ARG;
+  if (o->iterations > 0 && (!out_eigvec || !out_eigval || !out_weight))
+    return PBBSS_ERR_INVALID_ARG;
+  if (o->weight_mode != PBBSS_WEIGHT_PER_CLASS_MEAN && o->weight_mode != PBBSS_WEIGHT_UNIFORM)
+    return PBBSS_ERR_INVALID_ARG;
+  if (!(o->max_concentration > 0.0) || !(o->eigenvalue_eps >= 0.0) || !(o->norm_eps >= 0.0))
+    return PBBSS_ERR_INVALID_ARG;
+  if (D < 2 || D > 8 || K < 1 || K > 4) return PBBSS_ERR_UNSUPPORTED;
+  pbbss::BinghamArgs ba{};
+  ba.em.y = y;
+  ba.em.B = B;
+  ba.em.T = T;
+  ba.em.gamma0 = gamma0;
+  ba.em.in_weight = in_weight;
+  ba.em.wb = K;
+  ba.em.wk = 1;
+  ba.em.wt = 0;
+  ba.em.saliency = saliency;
+  ba.em.out_weight = out_weight;
+  ba.em.out_status = out_status;
+  ba.em.out_aff = out_affiliation;
+  ba.em.out_logpdf = out_log_pdf;
+  ba.em.iterations = o->iterations;
+  ba.em.weight_mode = o->weight_mode;
+  ba.em.layout = PBBSS_LAYOUT_TD;
+  ba.em.final_predict = o->final_predict && (out_affiliation || out_log_pdf);
+  ba.in_eigvec = static_cast<const double*>(in_eigvec);
+  ba.in_eigval = in_eigval;
+  ba.max_concentration = o->max_concentration;
+  ba.eigenvalue_eps = o->eigenvalue_eps;
+  ba.norm_eps = o->norm_eps;
+  ba.out_eigvec = static_cast<double*>(out_eigvec);
+  ba.out_eigval = out_eigval;
+  ba.out_lognorm = out_lognorm;
+  TimedRegion tr(h, as_stream(stream));
+  return pbbss::cb_launch(D, K, o->y_is_c128, ba, h->cfg, as_stream(stream));
+}
+
+PBBSS_API int pbbss_cbingham_find_eigenvalues(pbbss_handle_t h, const double* scatter_eigenvalues,
+                                              int64_t N, int D, double eigenvalue_eps,
+                                              double max_concentration, double* out_eigenvalues,
+                                              int32_t* out_status, void* stream) {
+  DeviceGuard device_guard(h);
+  if (!h || !scatter_eigenvalues || !out_eigenvalues || !out_status || N <= 0)
+    return PBBSS_ERR_INVALID_ARG;
+  if (!(max_concentration > 0.0) || !(eigenvalue_eps >= 0.0)) return PBBSS_ERR_INVALID_ARG;
+  if (D < 2 || D > 8) return PBBSS_ERR_UNSUPPORTED;
+  return pbbss::cb_solve_launch(D, scatter_eigenvalues, N, eigenvalue_eps, max_concentration,
+                                out_eigenvalues, out_status, h->cfg.num_cu, as_stream(stream));
 }
 
 PBBSS_API int pbbss_wmwf(pbbss_handle_t h, const void* target, const void* noise, int64_t N, int D,

@@ -9,6 +9,8 @@ from .complex_angular_central_gaussian import (
 from .cacgmm import CACGMM, CACGMMTrainer, sample_cacgmm
 from .complex_watson import ComplexWatson, ComplexWatsonTrainer
 from .cwmm import CWMM, CWMMTrainer
+from .complex_bingham import ComplexBingham, ComplexBinghamTrainer
+from .cbmm import CBMM, CBMMTrainer
 from .von_mises_fisher import VonMisesFisher, VonMisesFisherTrainer
 from .vmfmm import VMFMM, VMFMMTrainer
 from .gaussian import DiagonalGaussian, Gaussian, SphericalGaussian, GaussianTrainer
@@ -17,7 +19,8 @@ from .gcacgmm import GCACGMM, GCACGMMTrainer
 from .vmfcacgmm import VMFCACGMM, VMFCACGMMTrainer
 
 __all__ = [
-    'CACGMM', 'CACGMMTrainer', 'CWMM', 'CWMMTrainer',
+    'CACGMM', 'CACGMMTrainer', 'CWMM', 'CWMMTrainer', 'CBMM', 'CBMMTrainer',
+    'ComplexBingham', 'ComplexBinghamTrainer',
     'VonMisesFisher', 'VonMisesFisherTrainer', 'VMFMM', 'VMFMMTrainer',
     'Gaussian', 'DiagonalGaussian', 'SphericalGaussian', 'GaussianTrainer', 'GMM', 'GMMTrainer', 'GCACGMM', 'GCACGMMTrainer',
     'VMFCACGMM', 'VMFCACGMMTrainer',

@@ -44,6 +44,9 @@ def _raise_for_bits(bits, what):
     if bits & _lib.ST_EIG_NOCONV:
         # complex_angular_central_gaussian.py:94-110 (LinAlgError from eigh/eig)
         raise StatusLinAlgError(f'{what}: Hermitian eigensolver did not converge')
+    if bits & _lib.ST_SOLVE_NOCONV:
+        # complex_bingham.py:376-383 (only the complex Bingham kernels set this bit)
+        raise StatusLinAlgError(f'{what}: complex Bingham parameter solve did not converge')
 
 
 def _status_raise_em(status, what):
@@ -621,6 +624,64 @@ def cwmm_fit(y, K, spline, *, gamma0=None, model=None, iterations=100, saliency=
     if check_status and iterations > 0:
         return _checked_with_split_retry(launch, dev, 'CWMMTrainer.fit')
     return launch()
+
+
+def cbmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, weight_mode=0,
+             max_concentration=float('inf'), eigenvalue_eps=1e-8, norm_eps=1e-8, final_predict=False,
+             want_log_pdf=False, check_status=True):
+    """pbbss_cbmm_fit.  y (B,T,D) complex; gamma0 (B,K,T) f64 or
+    model=(eigvec (B,K,D,D) c128, eigval (B,K,D) f64, weight (B,K) f64).  norm_eps: the
+    de-duplication spacing of ln c (ComplexBingham.norm's eps; 0 keeps the eigenvalues)."""
+    t = _t()
+    dev = y.device
+    B, T, D = y.shape
+    f64 = t.float64
+    opts = _lib.CbmmOpts(
+        iterations=int(iterations), weight_mode=int(weight_mode),
+        y_is_c128=int(y.dtype == t.complex128),
+        final_predict=int(bool(final_predict or want_log_pdf)),
+        max_concentration=float(max_concentration), eigenvalue_eps=float(eigenvalue_eps),
+        norm_eps=float(norm_eps))
+    in_v = in_l = in_w = None
+    if model is not None:
+        in_v, in_l, in_w = model
+        assert in_v.shape == (B, K, D, D) and in_l.shape == (B, K, D) and in_w.shape == (B, K)
+    else:
+        assert gamma0.shape == (B, K, T) and gamma0.dtype == f64
+    out_v = t.empty((B, K, D, D), dtype=t.complex128, device=dev)
+    out_l = t.empty((B, K, D), dtype=f64, device=dev)
+    out_c = t.empty((B, K), dtype=f64, device=dev)
+    out_w = t.empty((B, K), dtype=f64, device=dev)
+    out_st = t.zeros((B, K), dtype=t.int32, device=dev)
+    out_aff = t.empty((B, K, T), dtype=f64, device=dev) if final_predict else None
+    out_lp = t.empty((B, K, T), dtype=f64, device=dev) if want_log_pdf else None
+    rc = _lib.load().pbbss_cbmm_fit(
+        _lib.handle(dev.index), _lib.ptr(y), B, T, D, K, _lib.ptr(gamma0), _lib.ptr(in_v),
+        _lib.ptr(in_l), _lib.ptr(in_w), _lib.ptr(saliency), ctypes.byref(opts), _lib.ptr(out_v),
+        _lib.ptr(out_l), _lib.ptr(out_c), _lib.ptr(out_w), _lib.ptr(out_st), _lib.ptr(out_aff),
+        _lib.ptr(out_lp), _lib.stream_ptr(dev.index))
+    _lib.check(rc, f'cbmm_fit(B={B},T={T},D={D},K={K})')
+    if check_status:
+        _status_raise_em(out_st, 'CBMMTrainer.fit')
+    return dict(eigvec=out_v, eigval=out_l, log_norm=out_c, weight=out_w, status=out_st,
+                affiliation=out_aff, log_pdf=out_lp)
+
+
+def cbingham_find_eigenvalues(scatter, eigenvalue_eps=1e-8, max_concentration=float('inf'),
+                              check_status=True):
+    """pbbss_cbingham_find_eigenvalues.  scatter (N,D) f64 device -> (lam (N,D), status (N,))."""
+    t = _t()
+    dev = scatter.device
+    N, D = scatter.shape
+    lam = t.empty((N, D), dtype=t.float64, device=dev)
+    st = t.zeros((N,), dtype=t.int32, device=dev)
+    rc = _lib.load().pbbss_cbingham_find_eigenvalues(
+        _lib.handle(dev.index), _lib.ptr(scatter), N, D, float(eigenvalue_eps),
+        float(max_concentration), _lib.ptr(lam), _lib.ptr(st), _lib.stream_ptr(dev.index))
+    _lib.check(rc, f'cbingham_find_eigenvalues(N={N},D={D})')
+    if check_status:
+        _status_raise_em(st, 'ComplexBinghamTrainer.find_eigenvalues_v3')
+    return lam, st
 
 
 def wmwf(target, noise, distortion_weight=1.0, frequency_dependent=False):
