@@ -44,12 +44,17 @@ def main():
     ap.add_argument('--size', type=int, default=1024)
     ap.add_argument('--shift', type=int, default=256)
     ap.add_argument('--iterations', type=int, default=100)
+    ap.add_argument('--init', choices=['random', 'deflation', 'flag'], default='random',
+                    help="affiliation initialisation: the trainer's uniform random draw, the "
+                         "device-side deflation seed (needs --size 512 or 1024: F in {257, 513}) or "
+                         "time segments (pb_bss_amd.initializer)")
     ap.add_argument('--beamformer', default='mvdr_souden',
                     help="recipe for get_bf_vector; the printed correlation compares with the source "
                          "image at sensor 0, so it is meaningful for distortionless recipes "
                          "('mvdr_souden', 'wmwf'), not for 'gev+ban' (free phase per bin)")
     args = ap.parse_args()
     import torch
+    from pb_bss_amd import initializer
     from pb_bss_amd.distribution import CACGMMTrainer
     from pb_bss_amd.extraction import (apply_beamforming_vector, get_bf_vector,
                                        get_power_spectral_density_matrix)
@@ -76,7 +81,14 @@ def main():
 
         Y = stft(x, args.size, args.shift, layout='f t d', dtype=np.complex64)   # (F, T, D)
         mark('stft')
-        masks = CACGMMTrainer().fit_predict(Y, num_classes=K, iterations=args.iterations)  # (F,K,T)
+        if args.init == 'random':
+            start = dict(num_classes=K)
+        elif args.init == 'deflation':                                       # (K,F,T) -> (F,K,T) view
+            start = dict(initialization=initializer.deflation.deflationSeed(Y, K).transpose(0, 1))
+        else:
+            start = dict(initialization=initializer.deterministic.flag(Y, K, permutation_free=True,
+                                                                       minimum=0.1 / K))
+        masks = CACGMMTrainer().fit_predict(Y, iterations=args.iterations, **start)  # (F,K,T)
         mark(f'cACGMM x{args.iterations}')
         solver = DHTVPermutationAlignment.from_stft_size(args.size)
         kft = solver(masks.transpose(0, 1).contiguous())                     # (K, F, T)

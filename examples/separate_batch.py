@@ -46,6 +46,10 @@ def main():
     ap.add_argument('--shard', choices=['bins', 'utterances'], default='bins',
                     help='multi-GPU: frequency bins of every utterance over the ranks (one mask '
                          'all-gather), or whole utterances per rank (no collective until the end)')
+    ap.add_argument('--init', choices=['random', 'deflation', 'flag'], default='random',
+                    help="affiliation initialisation: the generator's random one, the device-side "
+                         "deflation seed of the whole batch in one call (F must be 257 or 513), or "
+                         "time segments (pb_bss_amd.initializer)")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -62,6 +66,12 @@ def main():
     init = np.stack([d[1] for d in data])
     from pb_bss_amd import _lib
     Yd, initd = _lib.to_device(Y), _lib.to_device(init)
+    if args.init == 'deflation':    # (U, K, F, T) -> (U, F, K, T), computed where the STFT lies
+        from pb_bss_amd.initializer.deflation import deflationSeed
+        initd = deflationSeed(Yd, args.K).transpose(1, 2).contiguous()
+    elif args.init == 'flag':
+        from pb_bss_amd.initializer.deterministic import flag
+        initd = flag(Yd, args.K, permutation_free=True, minimum=0.1 / args.K).contiguous()
     separate(Yd[:1], initd[:1], 2, stft_size, sharded=False)  # warm-up
     torch.cuda.synchronize()
     t0 = time.perf_counter()

@@ -32,7 +32,8 @@ extern "C" {
 #endif
 
 #define PBBSS_VERSION 610 /* still 0.6.1 (the value is pinned by the symbol test): pbbss_cbmm_fit,
-                             pbbss_cbingham_find_eigenvalues, PBBSS_ST_SOLVE_NOCONV added since;
+                             pbbss_cbingham_find_eigenvalues, PBBSS_ST_SOLVE_NOCONV,
+                             pbbss_deflation_seed added since;
                              0.6.1: pbbss_select_reference_channel, pbbss_apply_beamforming_vector_shared;
                              0.6.0: pbbss_log_pdf_to_affiliation_inline_pa, D = 33 / 34 in pbbss_cacgmm_fit / _predict;
                              0.4.1: pbbss_set_dhtv_probe; 0.4.0: pbbss_split_reset, pbbss_set_spin_limit, pbbss_reference_channel_terms,
@@ -81,7 +82,9 @@ int pbbss_create(pbbss_handle_t* out, int device_id);
  * generic-size path at any D.  Watson mixture (pbbss_cwmm_fit): fused kernel for D <= 8, K <= 4,
  * generic-size path up to D = 32, K = 19.  Joint models (pbbss_joint_fit): D <= 32 (the spatial
  * half of 9 <= D <= 32, or of 7..8 classes, on the generic-size kernels; inline permutation
- * alignment for K <= 6), K <= 8 (bound of the spectral kernels).  LCMV: D <= 8. */
+ * alignment for K <= 6), K <= 8 (bound of the spectral kernels).  LCMV: D <= 8.  Deflation seed
+ * (pbbss_deflation_seed): fused for D <= 8, three launches per round around the generic
+ * eigensolver for 9 <= D <= 32; 2 <= K <= 19; any T > 2 neighbors. */
 int pbbss_destroy(pbbss_handle_t h);
 
 /* ------------------------------------------------------------------------- */
@@ -515,6 +518,40 @@ int pbbss_cbingham_find_eigenvalues(pbbss_handle_t h, const double* scatter_eige
                                     int64_t N, int D, double eigenvalue_eps,
                                     double max_concentration, double* out_eigenvalues,
                                     int32_t* out_status, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* I1  deflationSeed   initializer/deflation.py:6-89 (with _parameterized_vector_norm */
+/*     permutation_alignment.py:358-377, get_power_spectral_density_matrix          */
+/*     extraction/beamformer.py:59-160 and get_pca_vector :163-224).                */
+/* y (B,F,T,D) complex, raw; B utterances of F bins, each utterance independent.    */
+/* K - 1 deflation rounds: peak frame = arg-max of the saliency (per bin, or of the */
+/* mean over the F bins of the utterance when permutation_free; lowest index among  */
+/* ties, clipped to [neighbors, T-1-neighbors]), PSD of the 2 neighbors + 1 frames  */
+/* around it with the local saliencies as mask (normalised by max(sum, 1e-10)),     */
+/* its dominant eigenvector, similarity |z^H mode|^2 of every unit-normalised frame */
+/* = posterior of the class, saliency *= 1 - similarity.  Finalisation: last class  */
+/* 1 - sum, max(., eps), normalisation over the classes.                            */
+/* saliency f64 (B,F,T) or NULL (= |y|, used when round_begin == 0).                */
+/* Rounds [round_begin, round_end) of the K - 1 are run, then the finalisation if   */
+/* `finalize`; the whole seed is (0, K-1, 1).  A caller that edits similarities     */
+/* between rounds (similarity_transform) runs them one by one: round r leaves its   */
+/* similarity in out_posterior[:, r] and the deflated saliencies in saliency_state  */
+/* f64 (B,F,T), which the next call (round_begin > 0) reads.  saliency_state may be */
+/* NULL for a whole seed (private workspace of the handle).                         */
+/* out_posterior f64 (B,K,F,T); out_peak int32 (B,K-1,F) or NULL: the clipped peak  */
+/* frame of every round and bin.  Everything is stream-ordered: the cross-bin       */
+/* arg-max of the permutation-free form goes through device memory between          */
+/* launches (2 (K-1) + 1 of them), never through the host or a wait inside a kernel.*/
+/* 2 <= D <= 8: fused (all rounds of a bin in one launch when !permutation_free,    */
+/* frames and saliency row in LDS when they fit, in place otherwise); 9 <= D <= 32: */
+/* three launches per round around the generic eigensolver.  2 <= K <= 19.  Else    */
+/* PBBSS_ERR_UNSUPPORTED; T <= 2 neighbors: PBBSS_ERR_INVALID_ARG.                  */
+/* ------------------------------------------------------------------------- */
+int pbbss_deflation_seed(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int F, int T,
+                         int D, int K, const double* saliency, int permutation_free,
+                         int neighbors, double eps, int round_begin, int round_end,
+                         int finalize, double* saliency_state, double* out_posterior,
+                         int32_t* out_peak, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* N2/N3  Real-embedding mixture components: von Mises-Fisher and spherical      */

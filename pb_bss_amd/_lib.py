@@ -61,7 +61,7 @@ EXPORTS = (
     'pbbss_set_dhtv_team', 'pbbss_set_dhtv_probe', 'pbbss_stft_num_frames', 'pbbss_stft', 'pbbss_istft',
     'pbbss_pa_pairwise_mapping', 'pbbss_pa_compose_mapping', 'pbbss_pa_mapping_from_scores',
     'pbbss_gmm_fit', 'pbbss_gauss_full_fit', 'pbbss_gauss_full_log_pdf',
-    'pbbss_gmm_full_fit',
+    'pbbss_gmm_full_fit', 'pbbss_deflation_seed',
 )
 
 EMBED_VMF = 0
@@ -261,6 +261,8 @@ def load():
         lib.pbbss_cbmm_fit.argtypes = ([vp, vp, i64, i32, i32, i32] + [vp] * 5 +
                                        [ctypes.POINTER(CbmmOpts)] + [vp] * 8)
         lib.pbbss_cbingham_find_eigenvalues.argtypes = [vp, vp, i64, i32, dbl, dbl, vp, vp, vp]
+        lib.pbbss_deflation_seed.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, i32, dbl,
+                                             i32, i32, i32, vp, vp, vp, vp]
         for name in EXPORTS:
             fn = getattr(lib, name)
             if name not in ('pbbss_error_string',):

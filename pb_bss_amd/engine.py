@@ -684,6 +684,30 @@ def cbingham_find_eigenvalues(scatter, eigenvalue_eps=1e-8, max_concentration=fl
     return lam, st
 
 
+def deflation_seed(y, K, *, saliency=None, permutation_free=True, neighbors=5, eps=0.0,
+                   rounds=None, finalize=True, state=None, out=None, want_peak=False):
+    """pbbss_deflation_seed.  y (B,F,T,D) complex -> posterior (B,K,F,T) f64 (and the peak frames
+    (B,K-1,F) int32 with want_peak).  rounds=(begin, end) with `state` (B,F,T) and `out` runs a
+    part of the K - 1 deflation rounds (similarity_transform path); default: the whole seed."""
+    t = _t()
+    dev = y.device
+    B, F, T, D = y.shape
+    r0, r1 = (0, K - 1) if rounds is None else rounds
+    if out is None:
+        out = t.empty((B, K, F, T), dtype=t.float64, device=dev)
+    assert out.shape == (B, K, F, T) and out.dtype == t.float64
+    assert saliency is None or (saliency.shape == (B, F, T) and saliency.dtype == t.float64)
+    assert state is None or (state.shape == (B, F, T) and state.dtype == t.float64)
+    peak = t.empty((B, K - 1, F), dtype=t.int32, device=dev) if want_peak else None
+    rc = _lib.load().pbbss_deflation_seed(
+        _lib.handle(dev.index), _lib.ptr(y), int(y.dtype == t.complex128), B, F, T, D, int(K),
+        _lib.ptr(saliency), int(bool(permutation_free)), int(neighbors), float(eps), int(r0),
+        int(r1), int(bool(finalize)), _lib.ptr(state), _lib.ptr(out), _lib.ptr(peak),
+        _lib.stream_ptr(dev.index))
+    _lib.check(rc, f'deflation_seed(B={B},F={F},T={T},D={D},K={K})')
+    return (out, peak) if want_peak else out
+
+
 def wmwf(target, noise, distortion_weight=1.0, frequency_dependent=False):
     """pbbss_wmwf -> (filter matrix (N,D,D), snr_num (N,D), snr_den (N,D), status)."""
     t = _t()
