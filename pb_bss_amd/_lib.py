@@ -37,33 +37,6 @@ WEIGHT_SHARED_KT = 3  # weight_constant_axis=(-3,)
 LAYOUT_TD = 0
 LAYOUT_DT = 1
 
-EXPORTS = (
-    'pbbss_version', 'pbbss_error_string', 'pbbss_create', 'pbbss_destroy',
-    'pbbss_normalize_observation', 'pbbss_cacgmm_fit', 'pbbss_cacgmm_fit_shared',
-    'pbbss_cacgmm_predict',
-    'pbbss_cacg_m_step', 'pbbss_heev_batched', 'pbbss_psd', 'pbbss_gev', 'pbbss_gev_general',
-    'pbbss_comm_unique_id', 'pbbss_comm_create', 'pbbss_comm_destroy', 'pbbss_comm_info',
-    'pbbss_shard_bounds',
-    'pbbss_allgather_masks', 'pbbss_allgather_unpack', 'pbbss_estimate_mixture_weight',
-    'pbbss_log_pdf_to_affiliation', 'pbbss_log_pdf_to_affiliation_inline_pa',
-    'pbbss_solve', 'pbbss_mvdr_souden', 'pbbss_mvdr', 'pbbss_ban',
-    'pbbss_apply_beamforming_vector', 'pbbss_apply_beamforming_vector_shared',
-    'pbbss_select_reference_channel', 'pbbss_set_timing',
-    'pbbss_last_kernel_ms', 'pbbss_kernel_ms_lagged', 'pbbss_set_phase_profile',
-    'pbbss_dhtv_calculate_mapping', 'pbbss_apply_mapping', 'pbbss_cwmm_fit',
-    'pbbss_cbmm_fit', 'pbbss_cbingham_find_eigenvalues',
-    'pbbss_wmwf', 'pbbss_set_split_tail', 'pbbss_split_error', 'pbbss_split_reset', 'pbbss_set_spin_limit',
-    'pbbss_embed_log_pdf', 'pbbss_embed_fit', 'pbbss_vmfmm_fit', 'pbbss_joint_fit',
-    'pbbss_lcmv', 'pbbss_phase_correction', 'pbbss_snr_postfilter',
-    'pbbss_reference_channel_terms', 'pbbss_rank_one_approximation', 'pbbss_matvec',
-    'pbbss_distortionless_normalization', 'pbbss_zero_degree_normalization',
-    'pbbss_condition_covariance', 'pbbss_apply_online_beamforming_vector',
-    'pbbss_set_dhtv_team', 'pbbss_set_dhtv_probe', 'pbbss_stft_num_frames', 'pbbss_stft', 'pbbss_istft',
-    'pbbss_pa_pairwise_mapping', 'pbbss_pa_compose_mapping', 'pbbss_pa_mapping_from_scores',
-    'pbbss_gmm_fit', 'pbbss_gauss_full_fit', 'pbbss_gauss_full_log_pdf',
-    'pbbss_gmm_full_fit', 'pbbss_deflation_seed',
-)
-
 EMBED_VMF = 0
 EMBED_GAUSS_SPHERICAL = 1
 EMBED_GAUSS_FULL = 2
@@ -143,6 +116,100 @@ class MixOpts(ctypes.Structure):
     ]
 
 
+# ---- the C ABI as data: argument types of every export of include/pbbss.h ---------------
+# (tests/test_capi_symbols.py compares the kind of every parameter with the header's prototypes)
+vp, i32, u32, i64, dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_int64, ctypes.c_double
+P = ctypes.POINTER
+vpp, i32p, i64p, f32p = P(vp), P(i32), P(i64), P(ctypes.c_float)
+SIGNATURES = {
+    'pbbss_version': [],
+    'pbbss_error_string': [i32],
+    'pbbss_create': [vpp, i32],
+    'pbbss_destroy': [vp],
+    'pbbss_normalize_observation': [vp, vp, i32, i64, i32, i32, vp, vp],
+    'pbbss_cacgmm_fit': [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, P(EmOpts), vp, vp, vp,
+        vp, vp, vp, vp],
+    'pbbss_cacgmm_fit_shared': [vp, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, P(EmOpts),
+        vp, vp, vp, vp, vp, vp, vp],
+    'pbbss_cacgmm_predict': [vp, vp, i64, i32, i32, i32, vp, vp, vp, i64, i64, i64, vp, i32, i32,
+        dbl, vp, vp, vp, vp],
+    'pbbss_cacg_m_step': [vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, i32, dbl, vp, vp, vp, vp,
+        vp],
+    'pbbss_heev_batched': [vp, vp, i64, i32, vp, vp, vp, vp],
+    'pbbss_psd': [vp, vp, i32, i64, i32, i32, i32, vp, i32, vp, vp],
+    'pbbss_gev': [vp, vp, vp, i64, i32, vp, vp, vp],
+    'pbbss_gev_general': [vp, vp, vp, i64, i32, vp, vp, vp, vp],
+    'pbbss_comm_unique_id': [vp],
+    'pbbss_comm_create': [vp, vp, i32, i32],
+    'pbbss_comm_destroy': [vp],
+    'pbbss_comm_info': [vp, i32p, i32p],
+    'pbbss_shard_bounds': [i64, i32, i32, i64p, i64p],
+    'pbbss_allgather_masks': [vp, vp, i32, i64, i64, i64, vp, vp],
+    'pbbss_allgather_unpack': [vp, vp, i32, i32, i64, i64, i64, vp, vp],
+    'pbbss_estimate_mixture_weight': [vp, vp, vp, i64, i64, i32, i64, i32, i32, vp, vp],
+    'pbbss_log_pdf_to_affiliation': [vp, vp, i64, i32, i64, vp, i64, i64, i64, vp, dbl, vp, vp],
+    'pbbss_log_pdf_to_affiliation_inline_pa': [vp, vp, vp, i64, i32, i64, vp, i64, i64, i64, vp,
+        dbl, vp, vp, vp],
+    'pbbss_solve': [vp, vp, vp, i64, i32, i32, vp, vp, vp],
+    'pbbss_mvdr_souden': [vp, vp, vp, i64, i32, dbl, vp, vp, vp, vp, vp],
+    'pbbss_mvdr': [vp, vp, vp, i64, i32, vp, vp, vp],
+    'pbbss_ban': [vp, vp, vp, i64, i32, vp, vp],
+    'pbbss_apply_beamforming_vector': [vp, vp, vp, i32, i64, i32, i32, vp, vp],
+    'pbbss_apply_beamforming_vector_shared': [vp, vp, vp, i32, i64, i64, i32, i32, vp, vp],
+    'pbbss_select_reference_channel': [vp, vp, vp, vp, i64, i64, i32, i64, i64, dbl, vp, vp, vp,
+        vp],
+    'pbbss_set_timing': [vp, i32],
+    'pbbss_last_kernel_ms': [vp, f32p],
+    'pbbss_kernel_ms_lagged': [vp, i32, f32p],
+    'pbbss_set_phase_profile': [vp, vp],
+    'pbbss_dhtv_calculate_mapping': [vp, vp, i64, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp],
+    'pbbss_apply_mapping': [vp, vp, vp, i64, i32, i32, i32, vp, vp],
+    'pbbss_cwmm_fit': [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, P(CwmmOpts), vp, vp, vp, vp,
+        vp, vp, vp, vp, vp],
+    'pbbss_cbmm_fit': [vp, vp, i64, i32, i32, i32] + [vp] * 5 + [P(CbmmOpts)] + [vp] * 8,
+    'pbbss_cbingham_find_eigenvalues': [vp, vp, i64, i32, dbl, dbl, vp, vp, vp],
+    'pbbss_wmwf': [vp, vp, vp, i64, i32, dbl, i32, vp, vp, vp, vp, vp],
+    'pbbss_set_split_tail': [vp, i32],
+    'pbbss_split_error': [vp, i32p],
+    'pbbss_split_reset': [vp],
+    'pbbss_set_spin_limit': [vp, u32],
+    'pbbss_embed_log_pdf': [vp, vp, i32, i64, i64, i32, i32, i32, vp, vp, vp, vp],
+    'pbbss_embed_fit': [vp, vp, i32, i64, i64, i32, i32, i32, i32, vp, dbl, dbl, vp, vp, vp],
+    'pbbss_vmfmm_fit': [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, P(MixOpts), vp, vp, vp, vp,
+        vp, vp],
+    'pbbss_joint_fit': [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, P(MixOpts),
+        vp, vp, vp, vp, vp, vp, vp, vp],
+    'pbbss_lcmv': [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp],
+    'pbbss_phase_correction': [vp, vp, i64, i64, i32, i32, i32, vp, vp, vp],
+    'pbbss_snr_postfilter': [vp, vp, vp, vp, i64, i32, vp, vp],
+    'pbbss_reference_channel_terms': [vp, vp, vp, vp, i64, i32, vp, vp, vp],
+    'pbbss_rank_one_approximation': [vp, vp, vp, i64, i32, vp, vp],
+    'pbbss_matvec': [vp, vp, vp, i64, i32, vp, vp],
+    'pbbss_distortionless_normalization': [vp, vp, vp, vp, i64, i32, vp, vp],
+    'pbbss_zero_degree_normalization': [vp, vp, i64, i32, i32, vp, vp],
+    'pbbss_condition_covariance': [vp, vp, i64, i32, dbl, vp, vp],
+    'pbbss_apply_online_beamforming_vector': [vp, vp, vp, i32, i64, i32, i32, vp, vp],
+    'pbbss_set_dhtv_team': [vp, i32],
+    'pbbss_set_dhtv_probe': [vp, i32],
+    'pbbss_stft_num_frames': [i64, i32, i32, i32, i32, i32],
+    'pbbss_stft': [vp, vp, i32, i64, i64, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp],
+    'pbbss_istft': [vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, vp, i64, vp],
+    'pbbss_pa_pairwise_mapping': [vp, vp, vp, i64, i32, i64, i32, vp, vp, i32, i32, vp, vp, i64,
+        i64, vp, vp],
+    'pbbss_pa_compose_mapping': [vp, vp, i64, i32, i64, vp],
+    'pbbss_pa_mapping_from_scores': [vp, vp, i64, i32, i32, vp, vp, vp],
+    'pbbss_gmm_fit': [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, P(MixOpts), vp, vp, vp,
+        vp, vp, vp],
+    'pbbss_gauss_full_fit': [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp],
+    'pbbss_gauss_full_log_pdf': [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp],
+    'pbbss_gmm_full_fit': [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, P(MixOpts), vp, vp,
+        vp, vp, vp, vp, vp],
+    'pbbss_deflation_seed': [vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, i32, dbl, i32, i32, i32,
+        vp, vp, vp, vp],
+}
+EXPORTS = tuple(SIGNATURES)
+
+
 class PbbssError(RuntimeError):
     pass
 
@@ -168,105 +235,10 @@ def load():
         # runtimes and whichever initialises second reports "no ROCm-capable device".
         import torch  # noqa: F401
         lib = ctypes.CDLL(LIB_PATH)
-        vp, i32, i64, dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
-        lib.pbbss_version.restype = ctypes.c_int
-        lib.pbbss_error_string.restype = ctypes.c_char_p
-        lib.pbbss_error_string.argtypes = [i32]
-        lib.pbbss_create.argtypes = [ctypes.POINTER(vp), i32]
-        lib.pbbss_destroy.argtypes = [vp]
-        lib.pbbss_set_timing.argtypes = [vp, i32]
-        lib.pbbss_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-        lib.pbbss_kernel_ms_lagged.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_float)]
-        lib.pbbss_set_phase_profile.argtypes = [vp, vp]
-        lib.pbbss_set_split_tail.argtypes = [vp, i32]
-        lib.pbbss_set_dhtv_team.argtypes = [vp, i32]
-        lib.pbbss_set_dhtv_probe.argtypes = [vp, i32]
-        lib.pbbss_split_error.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
-        lib.pbbss_split_reset.argtypes = [vp]
-        lib.pbbss_set_spin_limit.argtypes = [vp, ctypes.c_uint]
-        lib.pbbss_stft_num_frames.argtypes = [i64, i32, i32, i32, i32, i32]
-        lib.pbbss_stft.argtypes = [vp, vp, i32, i64, i64, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]
-        lib.pbbss_istft.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, vp, i64, vp]
-        lib.pbbss_dhtv_calculate_mapping.argtypes = [vp, vp, i64, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp]
-        lib.pbbss_apply_mapping.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp]
-        lib.pbbss_pa_pairwise_mapping.argtypes = [vp, vp, vp, i64, i32, i64, i32, vp, vp, i32, i32,
-                                                  vp, vp, i64, i64, vp, vp]
-        lib.pbbss_pa_compose_mapping.argtypes = [vp, vp, i64, i32, i64, vp]
-        lib.pbbss_pa_mapping_from_scores.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
-        lib.pbbss_cwmm_fit.argtypes = [
-            vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(CwmmOpts), vp, vp,
-            vp, vp, vp, vp, vp, vp, vp]
-        lib.pbbss_normalize_observation.argtypes = [vp, vp, i32, i64, i32, i32, vp, vp]
-        lib.pbbss_cacgmm_fit.argtypes = [
-            vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp,
-            ctypes.POINTER(EmOpts), vp, vp, vp, vp, vp, vp, vp]
-        lib.pbbss_cacgmm_fit_shared.argtypes = [
-            vp, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
-            ctypes.POINTER(EmOpts), vp, vp, vp, vp, vp, vp, vp]
-        lib.pbbss_cacgmm_predict.argtypes = [
-            vp, vp, i64, i32, i32, i32, vp, vp, vp, i64, i64, i64, vp, i32, i32,
-            dbl, vp, vp, vp, vp]
-        lib.pbbss_cacg_m_step.argtypes = [
-            vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, i32, dbl, vp, vp, vp,
-            vp, vp]
-        lib.pbbss_heev_batched.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
-        lib.pbbss_psd.argtypes = [vp, vp, i32, i64, i32, i32, i32, vp, i32, vp, vp]
-        lib.pbbss_gev.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
-        lib.pbbss_gev_general.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp]
-        lib.pbbss_estimate_mixture_weight.argtypes = [vp, vp, vp, i64, i64, i32, i64, i32, i32, vp, vp]
-        lib.pbbss_log_pdf_to_affiliation.argtypes = [vp, vp, i64, i32, i64, vp, i64, i64, i64, vp, dbl, vp, vp]
-        lib.pbbss_log_pdf_to_affiliation_inline_pa.argtypes = [vp, vp, vp, i64, i32, i64, vp, i64, i64, i64, vp,
-                                                               dbl, vp, vp, vp]
-        lib.pbbss_comm_unique_id.argtypes = [vp]
-        lib.pbbss_comm_create.argtypes = [vp, vp, i32, i32]
-        lib.pbbss_comm_destroy.argtypes = [vp]
-        lib.pbbss_comm_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-        lib.pbbss_shard_bounds.argtypes = [i64, i32, i32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-        lib.pbbss_allgather_masks.argtypes = [vp, vp, i32, i64, i64, i64, vp, vp]
-        lib.pbbss_allgather_unpack.argtypes = [vp, vp, i32, i32, i64, i64, i64, vp, vp]
-        lib.pbbss_solve.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
-        lib.pbbss_mvdr_souden.argtypes = [vp, vp, vp, i64, i32, dbl, vp, vp, vp, vp, vp]
-        lib.pbbss_mvdr.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
-        lib.pbbss_wmwf.argtypes = [vp, vp, vp, i64, i32, dbl, i32, vp, vp, vp, vp, vp]
-        lib.pbbss_ban.argtypes = [vp, vp, vp, i64, i32, vp, vp]
-        lib.pbbss_apply_beamforming_vector.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp]
-        lib.pbbss_apply_beamforming_vector_shared.argtypes = [vp, vp, vp, i32, i64, i64, i32, i32,
-                                                              vp, vp]
-        lib.pbbss_select_reference_channel.argtypes = [vp, vp, vp, vp, i64, i64, i32, i64, i64, dbl,
-                                                       vp, vp, vp, vp]
-        lib.pbbss_embed_log_pdf.argtypes = [vp, vp, i32, i64, i64, i32, i32, i32, vp, vp, vp, vp]
-        lib.pbbss_embed_fit.argtypes = [vp, vp, i32, i64, i64, i32, i32, i32, i32, vp, dbl, dbl,
-                                        vp, vp, vp]
-        lib.pbbss_vmfmm_fit.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp,
-                                        ctypes.POINTER(MixOpts), vp, vp, vp, vp, vp, vp]
-        lib.pbbss_gmm_full_fit.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp,
-                                           ctypes.POINTER(MixOpts), vp, vp, vp, vp, vp, vp, vp]
-        lib.pbbss_gauss_full_fit.argtypes = [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp]
-        lib.pbbss_gauss_full_log_pdf.argtypes = [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp]
-        lib.pbbss_gmm_fit.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp,
-                                      ctypes.POINTER(MixOpts), vp, vp, vp, vp, vp, vp]
-        lib.pbbss_joint_fit.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp,
-                                        vp, vp, ctypes.POINTER(MixOpts), vp, vp, vp, vp, vp, vp,
-                                        vp, vp]
-        lib.pbbss_lcmv.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
-        lib.pbbss_phase_correction.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp, vp, vp]
-        lib.pbbss_snr_postfilter.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
-        lib.pbbss_reference_channel_terms.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp]
-        lib.pbbss_rank_one_approximation.argtypes = [vp, vp, vp, i64, i32, vp, vp]
-        lib.pbbss_matvec.argtypes = [vp, vp, vp, i64, i32, vp, vp]
-        lib.pbbss_distortionless_normalization.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
-        lib.pbbss_zero_degree_normalization.argtypes = [vp, vp, i64, i32, i32, vp, vp]
-        lib.pbbss_condition_covariance.argtypes = [vp, vp, i64, i32, dbl, vp, vp]
-        lib.pbbss_apply_online_beamforming_vector.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp, vp]
-        lib.pbbss_cbmm_fit.argtypes = ([vp, vp, i64, i32, i32, i32] + [vp] * 5 +
-                                       [ctypes.POINTER(CbmmOpts)] + [vp] * 8)
-        lib.pbbss_cbingham_find_eigenvalues.argtypes = [vp, vp, i64, i32, dbl, dbl, vp, vp, vp]
-        lib.pbbss_deflation_seed.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, i32, dbl,
-                                             i32, i32, i32, vp, vp, vp, vp]
-        for name in EXPORTS:
+        for name, argtypes in SIGNATURES.items():
             fn = getattr(lib, name)
-            if name not in ('pbbss_error_string',):
-                fn.restype = ctypes.c_int
+            fn.argtypes = argtypes
+            fn.restype = ctypes.c_char_p if name == 'pbbss_error_string' else ctypes.c_int
         _lib = lib
         return lib
 

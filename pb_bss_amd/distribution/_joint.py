@@ -1,5 +1,5 @@
 """Shared host logic of the joint spatial + spectral mixtures (GCACGMM, VMFCACGMM):
-argument handling around the single C-ABI call `pbbss_joint_fit` (csrc/capi.hip),
+argument handling around the single C-ABI call `pbbss_joint_fit` (csrc/capi_joint.hip),
 which enqueues, per EM iteration, the spectral log-pdf kernel, the joint cACG
 E/M/eigen kernel, the class-weight reduction and the spectral M-step.
 """

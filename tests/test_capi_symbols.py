@@ -112,3 +112,54 @@ def test_shard_bounds_c_abi_matches_python():
                 assert (lo.value, hi.value) == shard_bounds(F, world, rank), (F, world, rank)
     bad = ctypes.c_int64(0)
     assert lib.pbbss_shard_bounds(5, 2, 2, ctypes.byref(bad), ctypes.byref(bad)) != 0
+
+
+def header_prototypes():
+    """{function: [parameter declarations]} of every prototype of the header, comments stripped."""
+    txt = re.sub(r'/\*.*?\*/', '', header_text(), flags=re.S)
+    txt = re.sub(r'//[^\n]*', '', txt)
+    protos = {}
+    for name, params in re.findall(r'\b(pbbss_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', txt):
+        assert name not in protos, name
+        params = ' '.join(params.split())
+        protos[name] = [] if params in ('', 'void') else [p.strip() for p in params.split(',')]
+    return protos
+
+
+def c_parameter_kind(decl):
+    """'ptr', 'i32', 'i64', 'f64' or 'f32' of one C parameter declaration."""
+    if '*' in decl or re.search(r'\bpbbss_handle_t\b', decl):
+        return 'ptr'
+    words = decl.split()
+    assert len(words) >= 2, decl  # type and name
+    ctype = ' '.join(w for w in words[:-1] if w != 'const')
+    return {'int': 'i32', 'int32_t': 'i32', 'unsigned': 'i32', 'unsigned int': 'i32',
+            'int64_t': 'i64', 'double': 'f64', 'float': 'f32'}[ctype]
+
+
+def ctypes_parameter_kind(t):
+    import ctypes
+    if t is ctypes.c_void_p or t is ctypes.c_char_p or hasattr(t, 'contents'):
+        return 'ptr'
+    if t in (ctypes.c_int, ctypes.c_uint, ctypes.c_int32, ctypes.c_uint32):
+        assert ctypes.sizeof(t) == 4
+        return 'i32'
+    return {ctypes.c_int64: 'i64', ctypes.c_double: 'f64', ctypes.c_float: 'f32'}[t]
+
+
+def test_binding_signatures_match_header_prototypes():
+    """Every argument list of _lib.SIGNATURES has the parameter kinds (pointer, 32-bit int,
+    int64_t, double, float) of the prototype in include/pbbss.h.  Needs neither the built library
+    nor a GPU."""
+    from pb_bss_amd import _lib
+    protos = header_prototypes()
+    assert sorted(protos) == declared_functions()
+    assert sorted(_lib.SIGNATURES) == sorted(protos)
+    assert _lib.EXPORTS == tuple(_lib.SIGNATURES)
+    mismatches = []
+    for name, params in protos.items():
+        want = [c_parameter_kind(p) for p in params]
+        have = [ctypes_parameter_kind(t) for t in _lib.SIGNATURES[name]]
+        if want != have:
+            mismatches.append((name, want, have))
+    assert not mismatches, mismatches
