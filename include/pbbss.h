@@ -81,8 +81,11 @@ int pbbss_create(pbbss_handle_t* out, int device_id);
  * layout TD only for the fit).  1 <= K <= 6 classes on the fused kernels, 7 <= K <= 19 on the
  * generic-size path at any D.  Watson mixture (pbbss_cwmm_fit): fused kernel for D <= 8, K <= 4,
  * generic-size path up to D = 32, K = 19.  Joint models (pbbss_joint_fit): D <= 32 (the spatial
- * half of 9 <= D <= 32, or of 7..8 classes, on the generic-size kernels; inline permutation
- * alignment for K <= 6), K <= 8 (bound of the spectral kernels).  LCMV: D <= 8.  Deflation seed
+ * half of 9 <= D <= 32, or of 7..19 classes, on the generic-size kernels; inline permutation
+ * alignment for K <= 6), K <= 19 (more than eight classes: the class-tile spectral kernels of
+ * csrc/embed_wide.hip; not for opts->sharded fits).  Real-embedding mixtures and single fits
+ * (pbbss_vmfmm_fit, pbbss_gmm_fit, pbbss_embed_fit, pbbss_embed_log_pdf): 1 <= K <= 64,
+ * 1 <= E <= 256.  LCMV: D <= 8.  Deflation seed
  * (pbbss_deflation_seed): fused for D <= 8, three launches per round around the generic
  * eigensolver for 9 <= D <= 32; 2 <= K <= 19; any T > 2 neighbors. */
 int pbbss_destroy(pbbss_handle_t h);
@@ -557,7 +560,10 @@ int pbbss_deflation_seed(pbbss_handle_t h, const void* y, int y_is_c128, int64_t
 /* N2/N3  Real-embedding mixture components: von Mises-Fisher and spherical      */
 /* Gaussian (distribution/von_mises_fisher.py:33-144, gaussian.py:100-193).      */
 /* y (B,N,E) real, row-major, float32 or float64 (y_is_f64); 1 <= E <= 256,      */
-/* K <= 8.  `scale` (B,K) is the vMF concentration or the spherical covariance.   */
+/* 1 <= K <= 64 (K <= 8: one accumulator per class and lane, csrc/embed.hip;      */
+/* 9 <= K <= 64: class tiles on the FP64 matrix pipe, csrc/embed_wide.hip);       */
+/* PBBSS_ERR_UNSUPPORTED beyond.  `scale` (B,K) is the vMF concentration or the   */
+/* spherical covariance.                                                          */
 /* ------------------------------------------------------------------------- */
 #define PBBSS_EMBED_VMF 0             /* VonMisesFisher                       */
 #define PBBSS_EMBED_GAUSS_SPHERICAL 1 /* SphericalGaussian                    */
@@ -716,7 +722,11 @@ int pbbss_gmm_fit(pbbss_handle_t h, const void* y, int64_t B, int64_t N, int E, 
 /* in_scale is the `fixed_covariance` of gcacgmm.py:305-312.  saliency (F,T) or     */
 /* NULL.  Outputs as the inputs' shapes; out_status int32 (F,K), for GAUSS_FULL     */
 /* word 0 also carries PBBSS_ST_NOT_POSDEF of the spectral covariances;             */
-/* out_affiliation (F,K,T) = model.predict (final_predict).                         */
+/* out_affiliation (F,K,T) = model.predict (final_predict).  1 <= K <= 19: up to    */
+/* six classes on the fused spatial kernels, beyond on the generic-size ones; more  */
+/* than eight classes pair them with the class-tile spectral kernels                */
+/* (csrc/embed_wide.hip).  PBBSS_ERR_UNSUPPORTED: K > 19, opts->inline_pa with      */
+/* K > 6 (K! search), opts->sharded with K > 8.                                     */
 int pbbss_joint_fit(pbbss_handle_t h, const void* observation,
                     const void* embedding, int64_t F, int T, int D, int E, int K,
                     const double* gamma0, const void* in_eigvec,

@@ -955,6 +955,12 @@ PBBSS_API int pbbss_embed_log_pdf(pbbss_handle_t h, const void* y, int y_is_f64,
   if (!h || !y || !mean || !scale || !out_log_pdf) return PBBSS_ERR_INVALID_ARG;
   if (!embed_shape_ok(B, N, E, K)) return PBBSS_ERR_UNSUPPORTED;
   hipStream_t s = as_stream(stream);
+  if (K > pbbss::kEmbedMaxK) {  // class tiles on the matrix pipe (embed_wide.hip), no transposed copy
+    void* w = h->work.grow(pbbss::embed_wide_work_doubles(B, N, E, K) * 8);
+    if (!w) return PBBSS_ERR_HIP;
+    return pbbss::embed_wide_log_pdf(kind, y, y_is_f64, B, N, E, K, mean, scale, 1.0, N,
+                                     static_cast<double*>(w), out_log_pdf, h->cfg.lds_limit, s);
+  }
   const size_t esz = y_is_f64 ? 8 : 4;
   char* yd;
   double *offset, *prec;
@@ -1032,6 +1038,13 @@ PBBSS_API int pbbss_embed_fit(pbbss_handle_t h, const void* y, int y_is_f64, int
   if (!h || !y || !weights || !out_mean || !out_scale) return PBBSS_ERR_INVALID_ARG;
   if (!embed_shape_ok(B, N, E, K)) return PBBSS_ERR_UNSUPPORTED;
   hipStream_t s = as_stream(stream);
+  if (K > pbbss::kEmbedMaxK) {
+    void* w = h->work.grow(pbbss::embed_wide_work_doubles(B, N, E, K) * 8);
+    if (!w) return PBBSS_ERR_HIP;
+    return pbbss::embed_wide_fit(kind, y, y_is_f64, B, N, E, K, weights, normalize,
+                                 min_concentration, max_concentration, static_cast<double*>(w),
+                                 out_mean, out_scale, h->cfg.lds_limit, s);
+  }
   const size_t np = pbbss::embed_partial_doubles(B, N, E, K, nullptr);
   double *part, *yd, *yn;
   int rc = carve(h->work, [&](Carver& wc) {
@@ -1178,6 +1191,24 @@ static int embed_mixture_fit(pbbss_handle_t h, int kind, const void* y, int64_t 
   if (!out_mean || !out_scale || !out_weight) return PBBSS_ERR_INVALID_ARG;
   const bool vmf = (kind == PBBSS_EMBED_VMF);
   hipStream_t s = as_stream(stream);
+  if (K > pbbss::kEmbedMaxK) {
+    // 9 ... 64 classes: one fused sweep per iteration on class tiles (embed_wide.hip), for one big
+    // mixture and for many small ones alike
+    void* w = h->work.grow(pbbss::embed_wide_work_doubles(B, N, E, K) * 8);
+    if (!w) return PBBSS_ERR_HIP;
+    int rc0;
+    if (has_model) {
+      if ((rc0 = copy_d2d(out_mean, in_mean, (size_t)B * K * E * 8, s)) != PBBSS_OK) return rc0;
+      if ((rc0 = copy_d2d(out_scale, in_scale, (size_t)B * K * 8, s)) != PBBSS_OK) return rc0;
+      if ((rc0 = copy_d2d(out_weight, in_weight, (size_t)B * K * 8, s)) != PBBSS_OK) return rc0;
+    }
+    TimedRegion tr(h, s);
+    return pbbss::embed_wide_mixture(
+        kind, y, o->embedding_is_f64, B, N, E, K, gamma0, saliency, fixed_scale, o->iterations,
+        o->weight_mode, o->min_concentration, o->max_concentration, static_cast<double*>(w),
+        out_mean, out_scale, out_weight, o->final_predict ? out_affiliation : nullptr,
+        o->final_predict ? out_log_pdf : nullptr, h->cfg.lds_limit, s);
+  }
   // many small vMF mixtures (e.g. one per frequency bin): the persistent one-workgroup-per-mixture
   // kernel runs the whole loop in ONE launch (embed.hip: vmf_bin_em_kernel); a big mixture is
   // better off spread over the chip by the sweep + finalize pair below

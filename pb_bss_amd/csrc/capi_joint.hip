@@ -66,16 +66,16 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
   // (no residency gate: the member workgroups of the joint kernels never wait for each other --
   // the last arriver finishes the problem, run_joint_member in cacgmm_em.hpp)
   if (!h || !observation || !embedding || !o || F <= 0 || T <= 0) return PBBSS_ERR_INVALID_ARG;
-  // 9 <= D <= 32 or 7..8 classes: the spatial half runs on the generic-size kernels
+  // 9 <= D <= 32 or 7..19 classes: the spatial half runs on the generic-size kernels
   // (generic.hip), one E-step and one M-step launch group per iteration around the same spectral
-  // kernels
+  // kernels (more than eight classes: the class-tile kernels of embed_wide.hip)
   // ... and so does an utterance too long for the LDS-resident joint kernels (no HBM-scratch
   // variant of those): the generic kernels stream the frames (round 4; the reference has no
   // length limit)
   const size_t joint_lds = joint_lds_bytes(D, K, T, o->obs_is_c128);
   const bool gen = D > 8 || K > 6 || joint_lds > h->cfg.lds_limit;
-  if (D < 2 || K < 1 || K > pbbss::kEmbedMaxK || (gen && !pbbss::gen_supported(D, K)))
-    return PBBSS_ERR_UNSUPPORTED;
+  if (D < 2 || K < 1 || (gen && !pbbss::gen_supported(D, K))) return PBBSS_ERR_UNSUPPORTED;
+  const bool wide = K > pbbss::kEmbedMaxK;  // (K > 6 is always gen: K <= 19 by gen_supported)
   if (gen && (F > 65535 || (o->inline_pa && K > 6))) return PBBSS_ERR_UNSUPPORTED;
   const int64_t N = F * (int64_t)T;
   if (!embed_shape_ok(1, N, E, K)) return PBBSS_ERR_UNSUPPORTED;
@@ -90,6 +90,9 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
   // rank 0's first embedding row, broadcast once per fit by an all-reduce (the others contribute
   // zeros); the reduced tiles are all-reduced between the reduction and the finalize kernel.
   const bool sharded = o->sharded != 0 && o->iterations > 0;
+  // the class-tile fit takes its moments about the FIRST ROW OF THE RANK'S OWN block: partials of
+  // different ranks do not add up -- sharded fits stay at K <= 8
+  if (sharded && wide) return PBBSS_ERR_UNSUPPORTED;
   if (sharded && !h->comm) return PBBSS_ERR_INVALID_ARG;  // pbbss_comm_create first
   pbbss::PartialReduce all_ranks{
       [](void* ctx, double* buf, size_t count, hipStream_t st) -> int {
@@ -131,7 +134,8 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
   const bool rot = rot_allowed && !gen && !o->inline_pa && !(in_scale && gamma0) &&
                    o->iterations >= 2 &&
                    pbbss::joint_sweep_supported(o->kind, N, E, K, o->embedding_is_f64);
-  const size_t np0 = pbbss::embed_partial_doubles(1, N, E, K, nullptr);
+  const size_t np0 = wide ? pbbss::embed_wide_work_doubles(1, N, E, K)
+                          : pbbss::embed_partial_doubles(1, N, E, K, nullptr);
   const size_t npj = rot ? pbbss::joint_sweep_partial_doubles(o->kind, N, E, K, o->embedding_is_f64) : 0;
   const size_t np = np0 > npj ? np0 : npj;
   const size_t nfkt = (size_t)F * K * T;
@@ -147,7 +151,7 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
   double *lndet, *fin_tmp, *gshift, *g_mw, *g_cov, *g_inv, *g_logdet, *g_csum, *g_lp, *g_q;
   int32_t *gst, *g_zero;
   int rc = carve(h->work, [&](Carver& wc) {
-    yd = wc.take<char>((size_t)E * N * esz);
+    yd = wide ? nullptr : wc.take<char>((size_t)E * N * esz);  // (the class tiles read row-major)
     aff = wc.take<double>(nfkt);
     slp = wc.take<double>(nfkt);
     part = wc.take<double>(np);
@@ -179,8 +183,14 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
   if (rc != PBBSS_OK) return rc;
   if (hipMemsetAsync(gst, 0, 64, as_stream(stream)) != hipSuccess) return PBBSS_ERR_HIP;
   TimedRegion tr(h, s);
-  rc = pbbss::launch_embed_prepare(embedding, o->embedding_is_f64, 1, N, E, 0, yd, nullptr, s);
-  if (rc != PBBSS_OK) return rc;
+  if (wide && !g_full) {  // the Gaussians' common shift, once per fit
+    rc = pbbss::embed_wide_shift(o->kind, embedding, o->embedding_is_f64, 1, N, E, K, part, s);
+    if (rc != PBBSS_OK) return rc;
+  }
+  if (!wide) {
+    rc = pbbss::launch_embed_prepare(embedding, o->embedding_is_f64, 1, N, E, 0, yd, nullptr, s);
+    if (rc != PBBSS_OK) return rc;
+  }
   if (sharded && g_full) {
     // rank 0's first embedding row (converted to float64) on every rank
     if (h->comm_rank == 0) {
@@ -202,6 +212,10 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
   const bool fixed_scale = in_scale && has_gamma;
   bool mq_fresh = false;  // the full-covariance M-step also leaves the factorisation behind
   auto spectral = [&]() -> int {
+    if (wide && !g_full)
+      return pbbss::embed_wide_log_pdf(o->kind, embedding, o->embedding_is_f64, 1, N, E, K, out_mean,
+                                       out_scale, o->spectral_weight, T, part, slp,
+                                       h->cfg.lds_limit, s, /*have_shift=*/true);
     if (g_diag)
       return pbbss::launch_diag_estep(yd, o->embedding_is_f64, N, E, K, out_mean, out_scale,
                                       o->spectral_weight, T, dconst, slp, s);
@@ -224,6 +238,12 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
   };
   // generic-size spatial half: the posteriors of the current model (E-step of gcacgmm.py:66-117
   // with the spectral log-pdf as the extra exponent), then the cACG M-step from them
+  auto class_weights = [&](const double* a) -> int {
+    if (wide)
+      return pbbss::embed_wide_joint_weight(o->weight_mode, a, saliency, F, K, T, tmp, out_weight, s);
+    return pbbss::launch_joint_weight(o->weight_mode, a, saliency, F, K, T, tmp, out_weight, s,
+                                      reduce);
+  };
   const pbbss::GenInverseState g_state{g_inv, g_logdet, nullptr};
   auto gen_m_step = [&](const double* gam, bool fk_weights) -> int {
     int r = pbbss::launch_gen_mstep_cov(observation, o->obs_is_c128, F, T, D, K, g_mw, gam, saliency,
@@ -399,9 +419,7 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
       src = aff;
     }
     if (it == 0 || o->weight_mode != PBBSS_JOINT_WEIGHT_FK) {  // 'fk' weights: joint kernel
-      rc = pbbss::launch_joint_weight(o->weight_mode, src, saliency, F, K, T, tmp, out_weight, s,
-                                      reduce);
-      if (rc != PBBSS_OK) return rc;
+      if ((rc = class_weights(src)) != PBBSS_OK) return rc;
     }
     if (g_full) {
       // GaussianTrainer._fit(covariance_type='full') on the (1, F*T, E) embedding with the masked
@@ -412,6 +430,10 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
                                         gpart, out_mean, out_scale, mq, offset, nullptr, gst, s,
                                         sharded ? gshift : nullptr, reduce);
       mq_fresh = true;
+    } else if (wide) {
+      rc = pbbss::embed_wide_fit(o->kind, embedding, o->embedding_is_f64, 1, N, E, K, src, 0,
+                                 o->min_concentration, o->max_concentration, part, out_mean,
+                                 out_scale, h->cfg.lds_limit, s, T, saliency, /*have_shift=*/true);
     } else {
       rc = pbbss::launch_embed_fit(o->kind, embedding, o->embedding_is_f64, 1, N, E, K, src, T,
                                    saliency, o->min_concentration, o->max_concentration, -1, part,

@@ -4,6 +4,7 @@
 #include "pbbss.h"
 #include <mutex>
 #include "embed.hpp"
+#include "embed_wide.hpp"
 #include "em_launch.hpp"
 
 #define PBBSS_API extern "C" __attribute__((visibility("default")))
@@ -56,8 +57,11 @@ inline int copy_d2d(void* dst, const void* src, size_t bytes, hipStream_t s) {
                                                                                    : PBBSS_ERR_HIP;
 }
 
+// standalone embedding entry points: K <= kEmbedMaxK on the kernels of embed.hip, beyond on the
+// class tiles of embed_wide.hip
 inline bool embed_shape_ok(int64_t B, int64_t N, int E, int K) {
-  return B >= 1 && B <= 65535 && N >= 1 && E >= 1 && E <= kEmbedMaxE && K >= 1 && K <= kEmbedMaxK;
+  return B >= 1 && B <= 65535 && N >= 1 && E >= 1 && E <= kEmbedMaxE && K >= 1 &&
+         K <= kEmbedWideMaxK;
 }
 
 // Bump allocator over a slab (256-byte aligned pieces).  Without a base it only measures: take()

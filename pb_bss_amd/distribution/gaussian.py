@@ -48,7 +48,7 @@ class SphericalGaussian(_ProbabilisticModel):
         lead = tuple(mean.shape[:-1])
         y_lead = tuple(y.shape[:-2])
         K = int(np.prod(lead)) if lead else 1
-        if all(s == 1 for s in y_lead) and K <= 8:
+        if all(s == 1 for s in y_lead) and K <= engine.EMBED_MAX_CLASSES:
             out = engine.embed_log_pdf(y.reshape(1, N, E), _lib.EMBED_GAUSS_SPHERICAL,
                                        mean.reshape(1, K, E).contiguous(),
                                        cov.reshape(1, K).contiguous())
@@ -173,7 +173,7 @@ class GaussianTrainer:
             sal = _lib.to_device(saliency, t.float64).to(y.device)
         lead = np.broadcast_shapes(tuple(y.shape[:-2]), tuple(sal.shape[:-1]))
         K = int(np.prod(lead)) if lead else 1
-        if all(s == 1 for s in y.shape[:-2]) and K <= 8:
+        if all(s == 1 for s in y.shape[:-2]) and K <= engine.EMBED_MAX_CLASSES:
             mean, cov = engine.embed_fit(y.reshape(1, N, E), kind,
                                          sal.expand(*lead, N).reshape(1, K, N).contiguous())
         else:

@@ -816,6 +816,18 @@ def _real_embedding(y):
     return y.contiguous()
 
 
+JOINT_MAX_CLASSES = 19  # kGenMaxK (csrc/generic.hip): spatial half of pbbss_joint_fit
+EMBED_MAX_CLASSES = 64  # kEmbedWideMaxK (csrc/embed_wide.hpp); K <= 8 runs on csrc/embed.hip
+
+
+def _embed_check(rc, what, K):
+    if rc == _lib.ERR_UNSUPPORTED and K > EMBED_MAX_CLASSES:
+        raise NotImplementedError(
+            f'{what}: {K} classes -- the embedding kernels serve 1 <= K <= {EMBED_MAX_CLASSES} '
+            'classes and 1 <= E <= 256 features')
+    _lib.check(rc, what)
+
+
 def embed_log_pdf(y, kind, mean, scale):
     """pbbss_embed_log_pdf.  y (B,N,E) real; mean (B,K,E); scale (B,K) -> (B,K,N) f64."""
     t = _t()
@@ -826,7 +838,7 @@ def embed_log_pdf(y, kind, mean, scale):
     rc = _lib.load().pbbss_embed_log_pdf(
         _lib.handle(y.device.index), _lib.ptr(y), int(y.dtype == t.float64), B, N, E, K, int(kind),
         _lib.ptr(mean), _lib.ptr(scale), _lib.ptr(out), _lib.stream_ptr(y.device.index))
-    _lib.check(rc, f'embed_log_pdf(B={B},N={N},E={E},K={K})')
+    _embed_check(rc, f'embed_log_pdf(B={B},N={N},E={E},K={K})', K)
     return out
 
 
@@ -846,7 +858,7 @@ def embed_fit(y, kind, weights, *, normalize=False, min_concentration=1e-10,
         _lib.handle(y.device.index), _lib.ptr(y), int(y.dtype == t.float64), B, N, E, K, int(kind),
         int(bool(normalize)), _lib.ptr(weights), float(min_concentration),
         float(max_concentration), _lib.ptr(mean), _lib.ptr(scale), _lib.stream_ptr(y.device.index))
-    _lib.check(rc, f'embed_fit(B={B},N={N},E={E},K={K})')
+    _embed_check(rc, f'embed_fit(B={B},N={N},E={E},K={K})', K)
     return mean, scale
 
 
@@ -881,7 +893,7 @@ def vmfmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, w
         _lib.ptr(in_conc), _lib.ptr(in_w), _lib.ptr(saliency), ctypes.byref(opts),
         _lib.ptr(mean), _lib.ptr(conc), _lib.ptr(weight), _lib.ptr(aff), _lib.ptr(lp),
         _lib.stream_ptr(dev.index))
-    _lib.check(rc, f'vmfmm_fit(B={B},N={N},E={E},K={K})')
+    _embed_check(rc, f'vmfmm_fit(B={B},N={N},E={E},K={K})', K)
     return dict(mean=mean, concentration=conc, weight=weight, affiliation=aff, log_pdf=lp)
 
 
@@ -949,7 +961,7 @@ def gmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, wei
         _lib.ptr(in_cov), _lib.ptr(in_w), _lib.ptr(saliency), _lib.ptr(fixed_covariance),
         ctypes.byref(opts), _lib.ptr(mean), _lib.ptr(cov), _lib.ptr(weight), _lib.ptr(aff),
         _lib.ptr(lp), _lib.stream_ptr(dev.index))
-    _lib.check(rc, f'gmm_fit(B={B},N={N},E={E},K={K})')
+    _embed_check(rc, f'gmm_fit(B={B},N={N},E={E},K={K})', K)
     return dict(mean=mean, covariance=cov, weight=weight, affiliation=aff, log_pdf=lp)
 
 
@@ -1120,6 +1132,12 @@ def joint_fit(observation, embedding, K, kind, *, gamma0=None, model=None, itera
         _lib.ptr(in_scale), _lib.ptr(saliency), ctypes.byref(opts), _lib.ptr(eigvec),
         _lib.ptr(eigval), _lib.ptr(weight), _lib.ptr(mean), _lib.ptr(scale), _lib.ptr(status),
         _lib.ptr(aff), _lib.stream_ptr(dev.index))
+    if rc == _lib.ERR_UNSUPPORTED and (K > JOINT_MAX_CLASSES or (inline_pa and K > 6)
+                                       or (sharded and K > 8)):
+        raise NotImplementedError(
+            f'joint_fit(F={F},T={T},D={D},E={E},K={K}): the joint models serve 1 <= K <= '
+            f'{JOINT_MAX_CLASSES} classes (the generic-size spatial kernels), inline permutation '
+            'alignment 1 <= K <= 6, bin-sharded fits 1 <= K <= 8')
     _lib.check(rc, f'joint_fit(F={F},T={T},D={D},E={E},K={K})')
     if kind == _lib.EMBED_GAUSS_FULL and int(status[0, 0].item()) & _lib.ST_NOT_POSDEF:
         raise ValueError(  # sklearn's _compute_precision_cholesky via gaussian.py:26
