@@ -3,15 +3,15 @@ argument handling around the single C-ABI call `pbbss_joint_fit` (csrc/capi_join
 which enqueues, per EM iteration, the spectral log-pdf kernel, the joint cACG
 E/M/eigen kernel, the class-weight reduction and the spectral M-step.
 """
+import contextlib
+import threading
+
 import numpy as np
 
 from .. import _lib, engine
+from . import _mixture as mix
 from .complex_angular_central_gaussian import ComplexAngularCentralGaussian
-from .utils import as_result, random_affiliation
-
-
-import contextlib
-import threading
+from .utils import as_result
 
 _tls = threading.local()
 
@@ -54,15 +54,6 @@ def prepare(observation, embedding):
     return obs.contiguous(), emb.contiguous()
 
 
-def initial_affiliation(initialization, num_classes, F, T, device):
-    t = _lib.torch()
-    if initialization is None:
-        return random_affiliation((F, num_classes, T), device)  # global NumPy RNG, gcacgmm.py:186-190
-    g = _lib.to_device(initialization, t.float64).to(device)
-    assert g.shape[0] == F and g.shape[2] == T, (g.shape, F, T)
-    return g.contiguous()
-
-
 def fit(kind, observation, embedding, initialization, num_classes, iterations, saliency, *,
         covariance_norm, eigenvalue_floor, affiliation_eps, weight_constant_axis, spatial_weight,
         spectral_weight, inline_permutation_alignment, min_concentration=1e-10,
@@ -71,14 +62,14 @@ def fit(kind, observation, embedding, initialization, num_classes, iterations, s
     like_torch = _lib.is_torch(observation)
     t = _lib.torch()
     obs, emb = prepare(observation, embedding)
-    assert obs.shape[-1] > 1
     F, T, _ = obs.shape
-    gamma0 = initial_affiliation(initialization, num_classes, F, T, obs.device)
-    K = gamma0.shape[1]
+    if initialization is not None:  # (F, K, T) as it is: no broadcasting (gcacgmm.py:186-190)
+        assert initialization.shape[0] == F and initialization.shape[2] == T, (
+            initialization.shape, F, T)
+    p = mix.prepare_fit(obs, initialization, num_classes, saliency, weight_constant_axis,
+                        complex_input=True)
+    K, gamma0, sal = p.K, p.gamma0.contiguous(), p.saliency
     assert iterations > 0, iterations
-    sal = None
-    if saliency is not None:
-        sal = _lib.to_device(saliency, t.float64).to(obs.device).expand(F, T).contiguous()
     fixed = None
     if fixed_scale is not None:
         fixed = _lib.to_device(fixed_scale, t.float64).to(obs.device).contiguous()

@@ -19,25 +19,24 @@ Arithmetic is float64 on the device for complex64 and complex128 input alike
 (SURVEY.md section 7); outputs are float64 / complex128.
 """
 from dataclasses import dataclass, field
-from operator import xor
 
 import numpy as np
 
 from .. import _lib, engine
+from . import _mixture as mix
 from .complex_angular_central_gaussian import (
     ComplexAngularCentralGaussian,
     ComplexAngularCentralGaussianTrainer,
     _complex_device,
     normalize_observation,
 )
-from .mixture_model_utils import (  # noqa: F401  (log_pdf_to_affiliation: the reference re-exports it)
-    _host_estimate_mixture_weight,
+from .mixture_model_utils import (  # noqa: F401  (the reference's cacgmm.py re-exports them)
     apply_inline_permutation_alignment,
     estimate_mixture_weight,
     log_pdf_to_affiliation,
 )
-from .utils import (_ProbabilisticModel, as_result, random_affiliation, reference_arithmetic,
-                    reference_single, to_single)
+from .utils import (_ProbabilisticModel, as_result, reference_arithmetic, reference_single,
+                    to_single)
 
 __all__ = ['CACGMM', 'CACGMMTrainer', 'normalize_observation', 'sample_cacgmm']
 
@@ -73,10 +72,17 @@ def _weight_for_predict(weight, indep, K, N, device):
     """Expand a reference-shaped weight ((..., K, 1), (K, 1), (..., 1, K, N), ...)
     to (B, K) or (B, K, N) float64 on the device."""
     t = _lib.torch()
-    w = _lib.to_device(weight, t.float64).to(device)
-    if w.shape[-1] == 1:
-        return w.expand(*indep, K, 1).reshape(-1, K).contiguous()
-    return w.expand(*indep, K, N).reshape(-1, K, N).contiguous()
+    if weight.shape[-1] == 1:
+        return mix.flatten_param(weight, indep, (K, 1), t.float64, device).reshape(-1, K)
+    return mix.flatten_param(weight, indep, (K, N), t.float64, device)
+
+
+def _cacg_parameters(cacg, indep, K, device=None):
+    """-> eigenvectors (B, K, D, D) complex128, eigenvalues (B, K, D) float64"""
+    t = _lib.torch()
+    D = cacg.covariance_eigenvectors.shape[-1]
+    return (mix.flatten_param(cacg.covariance_eigenvectors, indep, (K, D, D), t.complex128, device),
+            mix.flatten_param(cacg.covariance_eigenvalues, indep, (K, D), t.float64, device))
 
 
 def _activity(mask, indep, K, N, device):
@@ -85,9 +91,8 @@ def _activity(mask, indep, K, N, device):
     t = _lib.torch()
     is_bool = (mask.dtype == t.bool) if _lib.is_torch(mask) else (mask.dtype == bool)
     assert is_bool, mask.dtype  # reference: mixture_model_utils.py:40
-    m = _lib.to_device(mask).to(device).to(t.uint8)
-    assert tuple(m.shape[-2:]) == (K, N), (m.shape, K, N)
-    return m.expand(*indep, K, N).reshape(-1, K, N).contiguous()
+    assert tuple(mask.shape[-2:]) == (K, N), (mask.shape, K, N)
+    return mix.flatten_param(mask, indep, (K, N), t.uint8, device)
 
 
 def _stepwise_graph_enabled():
@@ -147,12 +152,8 @@ class CACGMM(_ProbabilisticModel):
 
     def _device_e_step(self, y_flat, indep, N, layout, source_activity_mask,
                        affiliation_eps, want_q=False, want_log_pdf=False):
-        t = _lib.torch()
-        vec = _lib.to_device(self.cacg.covariance_eigenvectors, t.complex128)
-        val = _lib.to_device(self.cacg.covariance_eigenvalues, t.float64)
-        K, D = vec.shape[-3], vec.shape[-1]
-        vb = vec.expand(*indep, K, D, D).reshape(-1, K, D, D).contiguous()
-        lb = val.expand(*indep, K, D).reshape(-1, K, D).contiguous()
+        K = self.cacg.covariance_eigenvectors.shape[-3]
+        vb, lb = _cacg_parameters(self.cacg, indep, K)
         w = _weight_for_predict(self.weight, indep, K, N, y_flat.device)
         act = _activity(source_activity_mask, indep, K, N, y_flat.device)
         aff, q, lp = engine.em_predict(
@@ -201,13 +202,6 @@ class CACGMMTrainer:
         the global NumPy RNG exactly as the reference, cacgmm.py:208-209).
         Returns a CACGMM (NumPy fields for NumPy input, torch for torch input).
         """
-        assert xor(initialization is None, num_classes is None), (
-            "Incompatible input combination. "
-            "Exactly one of the two inputs has to be None: "
-            f"{initialization is None} xor {num_classes is None}"
-        )
-        like_torch = _lib.is_torch(y)
-        t = _lib.torch()
         # arithmetic 'reference': a complex64 observation with an array initialisation is what the
         # reference computes in single precision (cacgmm.py:226-227) -> packed-FP32 kernel
         packed32 = (reference_arithmetic() and initialization is not None
@@ -221,42 +215,18 @@ class CACGMMTrainer:
                                       initialization.cacg.covariance_eigenvalues, saliency)
         else:
             single = initialization is not None and reference_single(y, saliency)
-        y = _complex_device(y)
-        assert y.shape[-1] > 1, y.shape
+        p = mix.prepare_fit(y, initialization, num_classes, saliency, weight_constant_axis,
+                            complex_input=True, model_type=CACGMM)
         assert iterations > 0, iterations
-        *indep, N, D = y.shape
-        indep = tuple(indep)
+        y, indep, N, D, like_torch = p.y, p.indep, p.N, p.D, p.like_torch
+        gamma0, sal, weight_constant_axis = p.gamma0, p.saliency, p.weight_constant_axis
         dev = y.device
-
-        model = None
-        gamma0 = None
-        if initialization is None:
-            assert num_classes is not None, num_classes
-            shape = (*indep, num_classes, N)
-            # global NumPy RNG, as the reference (utils.random_affiliation)
-            gamma0 = random_affiliation(shape, dev)
-        elif isinstance(initialization, CACGMM):
-            num_classes = initialization.cacg.covariance_eigenvectors.shape[-3]
-            model = initialization
-        elif isinstance(initialization, np.ndarray) or _lib.is_torch(initialization):
-            num_classes = initialization.shape[-2]
-            assert num_classes > 1, num_classes
-            shape = (*indep, num_classes, N)
-            assert initialization.ndim == len(shape), (initialization.shape, shape)
-            assert tuple(initialization.shape[-2:]) == shape[-2:], (
-                initialization.shape, shape)
-            gamma0 = _lib.to_device(initialization, t.float64).to(dev).expand(shape)
-        else:
-            raise TypeError('No sufficient initialization.')
-        K = num_classes
-
-        if isinstance(weight_constant_axis, list):
-            weight_constant_axis = tuple(weight_constant_axis)
+        model = initialization if gamma0 is None else None
+        K = initialization.cacg.covariance_eigenvectors.shape[-3] if model is not None else p.K
         if source_activity_mask is not None:
             assert tuple(source_activity_mask.shape[-2:]) == (K, N), (
                 source_activity_mask.shape, indep, K, N)
-            if gamma0 is not None and not isinstance(initialization, CACGMM) \
-                    and initialization is not None:
+            if model is None and initialization is not None:
                 assert tuple(source_activity_mask.shape) == tuple(initialization.shape), (
                     source_activity_mask.shape, initialization.shape)
         assert K < 20, f'num_classes: {K}, sure?'
@@ -264,8 +234,7 @@ class CACGMMTrainer:
         # (D = 33, 34 -- admitted by the sanity assert above -- run on 36-wide padded tiles of the
         # generic-size kernels since round 6: csrc/generic.hip)
 
-        ndim = len(indep) + 2
-        mode = self._weight_mode(weight_constant_axis, ndim)
+        mode = self._weight_mode(weight_constant_axis, p.ndim)
         # _weight_hook (sharding.shared_weight_allreduce): the mixture weights are estimated over
         # bins that live on other ranks too -> step-wise loop with the hook between E and M
         fused = (mode is not None and inline_permutation_aligner is None and _weight_hook is None)
@@ -275,10 +244,6 @@ class CACGMMTrainer:
             fused = (w is not None and w.shape[-1] == 1)
 
         act = _activity(source_activity_mask, indep, K, N, dev)
-        sal = None
-        if saliency is not None:
-            sal = _lib.to_device(saliency, t.float64).to(dev).expand(*indep, N)
-            sal = sal.reshape(-1, N).contiguous()
 
         if fused:
             if packed32 and D <= 8 and K <= 6:
@@ -303,7 +268,7 @@ class CACGMMTrainer:
                 y.reshape(-1, N, D), indep, K, gamma0, model, iterations, sal,
                 act, mode, covariance_norm, affiliation_eps, eigenvalue_floor,
                 hermitize, like_torch, final_predict=_with_affiliation), single, mode)
-        smode = self._shared_mode(weight_constant_axis, ndim)
+        smode = self._shared_mode(weight_constant_axis, p.ndim)
         if smode is not None and inline_permutation_aligner is None and _weight_hook is None:
             out = self._fit_shared(
                 y.reshape(-1, N, D), indep, K, gamma0, model, iterations, sal, act, smode,
@@ -336,30 +301,10 @@ class CACGMMTrainer:
             return model
         return model, to_single(aff)
 
-    @staticmethod
-    def _weight_mode(axis, ndim):
-        """Map weight_constant_axis to the kernel's built-in modes, or None."""
-        if isinstance(axis, int):
-            if axis % ndim - ndim == -2:
-                return _lib.WEIGHT_UNIFORM  # mixture_model_utils.py:180-183
-            axis = (axis,)
-        axes = {a % ndim - ndim for a in axis}
-        if axes == {-1}:
-            return _lib.WEIGHT_PER_CLASS_MEAN
-        return None
-
-    @staticmethod
-    def _shared_mode(axis, ndim):
-        """weight_constant_axis that averages the weights over the last independent axis (the
-        frequency bins): (-3,) and (-3, -1) run in the cooperative kernel."""
-        if isinstance(axis, int):
-            axis = (axis,)
-        axes = {a % ndim - ndim for a in axis}
-        if ndim >= 3 and axes == {-3}:
-            return _lib.WEIGHT_SHARED_KT
-        if ndim >= 3 and axes == {-3, -1}:
-            return _lib.WEIGHT_SHARED_K
-        return None
+    # weight_constant_axis -> the kernels' weight modes, mixture weights on the device
+    _weight_mode = staticmethod(mix.fused_weight_mode)
+    _shared_mode = staticmethod(mix.shared_weight_mode)
+    _device_weight = staticmethod(mix.kernel_weight)
 
     # ----------------------------------------------------- weights shared over the bins
     def _fit_shared(self, yb, indep, K, gamma0, model, iterations, sal, act, smode,
@@ -381,12 +326,8 @@ class CACGMMTrainer:
                 w = w.expand(*outer, 1, K, Nw)
             except RuntimeError:
                 return None  # weights of another shape: the step-wise loop takes any broadcast
-            vec = _lib.to_device(model.cacg.covariance_eigenvectors, t.complex128).to(yb.device)
-            val = _lib.to_device(model.cacg.covariance_eigenvalues, t.float64).to(yb.device)
-            dev_model = (
-                vec.expand(*indep, K, D, D).reshape(B, K, D, D).contiguous(),
-                val.expand(*indep, K, D).reshape(B, K, D).contiguous(),
-                w.reshape((G, K, N) if Nw == N else (G, K)).contiguous())
+            dev_model = (*_cacg_parameters(model.cacg, indep, K, yb.device),
+                         w.reshape((G, K, N) if Nw == N else (G, K)).contiguous())
         else:
             g0 = gamma0.reshape(B, K, N).contiguous()
         r = engine.em_fit_shared(
@@ -416,13 +357,8 @@ class CACGMMTrainer:
         dev_model = None
         g0 = None
         if model is not None:
-            vec = _lib.to_device(model.cacg.covariance_eigenvectors, t.complex128)
-            val = _lib.to_device(model.cacg.covariance_eigenvalues, t.float64)
-            w = _lib.to_device(model.weight, t.float64)
-            dev_model = (
-                vec.expand(*indep, K, D, D).reshape(B, K, D, D).contiguous(),
-                val.expand(*indep, K, D).reshape(B, K, D).contiguous(),
-                w.expand(*indep, K, 1).reshape(B, K).contiguous())
+            dev_model = (*_cacg_parameters(model.cacg, indep, K),
+                         mix.flatten_param(model.weight, indep, (K, 1), t.float64).reshape(B, K))
         else:
             g0 = gamma0.reshape(B, K, N).contiguous()
         r = engine.em_fit(
@@ -431,12 +367,8 @@ class CACGMMTrainer:
             weight_mode=mode, affiliation_eps=affiliation_eps,
             eigenvalue_floor=eigenvalue_floor, hermitize=hermitize,
             layout=_lib.LAYOUT_TD, final_predict=final_predict, precision=precision)
-        if mode == _lib.WEIGHT_UNIFORM:
-            weight = t.full((K, 1), 1.0 / K, dtype=t.float64, device=yb.device)
-        else:
-            weight = r['weight'].reshape(*indep, K, 1)
         out = CACGMM(
-            weight=as_result(weight, like_torch),
+            weight=as_result(mix.fused_weight(mode, r['weight'], indep, K, yb.device), like_torch),
             cacg=ComplexAngularCentralGaussian(
                 covariance_eigenvectors=as_result(
                     r['eigvec'].reshape(*indep, K, D, D), like_torch),
@@ -447,35 +379,6 @@ class CACGMMTrainer:
         return out
 
     # --------------------------------------------------------------- stepwise
-    @staticmethod
-    def _device_weight(aff, sal, weight_constant_axis, indep):
-        """estimate_mixture_weight (mixture_model_utils.py:133-203) on the device for the
-        axis sets that occur in practice: the trailing `r` independent axes and / or the frame
-        axis.  aff (*indep, K, N) device tensor, sal (*indep, N) or None.
-        Returns the reference-shaped weight (keepdims) as a device tensor, or None if the axis
-        set is not of that form (the caller then takes the host formula)."""
-        nd = len(indep) + 2
-        axes = ((weight_constant_axis,) if isinstance(weight_constant_axis, int)
-                else tuple(weight_constant_axis))
-        axes = sorted({a % nd for a in axes})
-        if nd - 2 in axes:  # the class axis: only the scalar form -2 is defined (handled earlier)
-            return None
-        red_n = (nd - 1) in axes
-        ind_axes = [a for a in axes if a < nd - 2]
-        r = len(ind_axes)
-        if ind_axes != list(range(nd - 2 - r, nd - 2)):
-            return None  # not a trailing block of independent axes
-        K, N = aff.shape[-2:]
-        Bi = int(np.prod(indep[len(indep) - r:], dtype=np.int64)) if r else 1
-        Bo = int(np.prod(indep[:len(indep) - r], dtype=np.int64)) if len(indep) > r else 1
-        a4 = aff.reshape(Bo, Bi, K, N).contiguous()
-        s3 = None if sal is None else sal.reshape(Bo, Bi, N).contiguous()
-        w = engine.estimate_mixture_weight(a4, s3, reduce_inner=r > 0, reduce_n=red_n)
-        if w is None:  # not served (saliency with K > 16): the caller takes the host formula
-            return None
-        shape = list(indep[:len(indep) - r]) + [1] * r + [K, 1 if red_n else N]
-        return w.reshape(shape)
-
     @staticmethod
     def _replay_iterations(t, e_step, m_step, vec, val, weight, m_status, aligner_status, count):
         """Capture one E + M iteration that reads the model from static tensors and writes the new
@@ -527,7 +430,8 @@ class CACGMMTrainer:
         (`pbbss_estimate_mixture_weight`) and, optionally, the device permutation aligner in
         between.  Everything stays on the device: no host round trip inside the loop.
         (`hermitize` is accepted for signature compatibility: the device M-step accumulates the
-        Hermitian-packed covariance, which is Hermitian by construction.)"""
+        Hermitian-packed covariance, which is Hermitian by construction; `saliency` likewise: the
+        loop works with `sal`, its (B, N) device form.)"""
         t = _lib.torch()
         B, N, D = yb.shape
         dev = yb.device
@@ -539,9 +443,7 @@ class CACGMMTrainer:
             # normalise in float64 (the reference keeps the input precision)
             yn, y_layout = engine.normalize_observation(yb), _lib.LAYOUT_DT  # (B, D, N)
         shape = (*indep, K, N)
-        sal_dev = None
-        if saliency is not None:
-            sal_dev = _lib.to_device(saliency, t.float64).to(dev).expand(*indep, N).contiguous()
+        sal_dev = None if sal is None else sal.reshape(*indep, N)
         vec = val = weight = None
         if model is None:
             aff = gamma0.reshape(shape).to(t.float64).contiguous()
@@ -550,47 +452,34 @@ class CACGMMTrainer:
             vec = _lib.to_device(model.cacg.covariance_eigenvectors, t.complex128).to(dev)
             val = _lib.to_device(model.cacg.covariance_eigenvalues, t.float64).to(dev)
             weight = _lib.to_device(model.weight, t.float64).to(dev)
-        device_aligner = aligner is not None and type(aligner).__module__.startswith('pb_bss_amd')
         aligner_status = []  # device status words of the aligner, read once after the loop
         m_status = []
-        host_excursion = [not device_aligner and aligner is not None]  # any step that leaves the device
+        # any step that leaves the device (a foreign aligner, the host formula of the weights)
+        host_excursion = [aligner is not None and not mix.is_device_aligner(aligner)]
+
+        def left_device():
+            host_excursion[0] = True
 
         def e_step(vec, val, weight):
             w = _weight_for_predict(weight, indep, K, N, dev)
             aff, q, _ = engine.em_predict(
-                yn, vec.expand(*indep, K, D, D).reshape(B, K, D, D).contiguous(),
-                val.expand(*indep, K, D).reshape(B, K, D).contiguous(), w,
+                yn, mix.flatten_param(vec, indep, (K, D, D), t.complex128),
+                mix.flatten_param(val, indep, (K, D), t.float64), w,
                 activity=act, layout=y_layout,
                 affiliation_eps=affiliation_eps, want_q=True)
             aff, q = aff.reshape(shape), q.reshape(shape)
             if aligner is not None:
-                if device_aligner:
-                    aff, q = apply_inline_permutation_alignment(
-                        affiliation=aff, quadratic_form=q,
-                        weight_constant_axis=weight_constant_axis, aligner=aligner,
-                        status_out=aligner_status)
-                else:  # a foreign (NumPy) aligner object: the one host excursion left
-                    a_h, q_h = apply_inline_permutation_alignment(
-                        affiliation=_lib.to_host(aff), quadratic_form=_lib.to_host(q),
-                        weight_constant_axis=weight_constant_axis, aligner=aligner)
-                    aff = _lib.to_device(a_h, t.float64, device=dev)
-                    q = _lib.to_device(q_h, t.float64, device=dev)
+                aff, q = mix.align(aligner, aff, weight_constant_axis, quadratic_form=q,
+                                   status_out=aligner_status)
             return aff, q
 
         def m_step(aff, q):
             weight = None
             if weight_hook is not None:
                 weight = weight_hook(aff, sal_dev)  # e.g. an all-reduce over the ranks' bins
-            elif isinstance(weight_constant_axis, int) and \
-                    weight_constant_axis % len(shape) - len(shape) == -2:
-                weight = t.full((K, 1), 1.0 / K, dtype=t.float64, device=dev)  # :180-183
-            else:
-                weight = self._device_weight(aff, sal_dev, weight_constant_axis, indep)
-            if weight is None:  # exotic axis sets: the NumPy formula
-                host_excursion[0] = True
-                weight = _lib.to_device(_host_estimate_mixture_weight(
-                    _lib.to_host(aff), None if sal_dev is None else _lib.to_host(sal_dev),
-                    weight_constant_axis), t.float64, device=dev)
+            if weight is None:
+                weight = mix.device_weight(aff, sal_dev, weight_constant_axis, indep,
+                                           on_host=left_device)
             masked = aff if sal_dev is None else aff * sal_dev[..., None, :]
             # status words of the M-step: queued like the aligner's, one read-back after the loop
             vec, val, _, st = engine.cacg_m_step(

@@ -10,19 +10,18 @@ with iterations = 0 / 1, plus the softmax and weight kernels).
 """
 from dataclasses import dataclass
 from functools import cached_property
-from operator import xor
 
 import numpy as np
 
 from .. import _lib, engine
-from .cacgmm import CACGMMTrainer
+from . import _mixture as mix
 from .complex_bingham import ComplexBingham, ComplexBinghamTrainer, normalize_observation  # noqa: F401
 from .mixture_model_utils import (  # noqa: F401  (re-exported like the reference's cbmm.py)
     apply_inline_permutation_alignment,
     estimate_mixture_weight,
     log_pdf_to_affiliation,
 )
-from .utils import _ProbabilisticModel, as_result, random_affiliation
+from .utils import _ProbabilisticModel, as_result
 
 __all__ = ['CBMM', 'CBMMTrainer']
 
@@ -36,26 +35,16 @@ def _check_shape(D, K):
         raise NotImplementedError(f'CBMM: K = {K} classes, the kernel serves K <= {MAX_CLASSES}')
 
 
-def _broadcast_weight(w, indep, shape_len):
-    """reference-shaped weight (..., K, 1 or T) -> (B or 1, K, 1 or T) for the softmax kernel"""
-    while w.ndim < shape_len:
-        w = w.unsqueeze(0)
-    if any(a != 1 for a in w.shape[:-2]):
-        return w.expand(*indep, *w.shape[-2:]).reshape(-1, *w.shape[-2:])
-    return w.reshape(1, *w.shape[-2:])
+def _log_pdf(yb, K, V, lam, ones_w):
+    """Class log-pdfs (B, K, N): `pbbss_cbmm_fit` with iterations = 0 and unit weights."""
+    return engine.cbmm_fit(yb, K, model=(V, lam, ones_w), iterations=0,
+                           want_log_pdf=True)['log_pdf']
 
 
 @dataclass
 class CBMM(_ProbabilisticModel):
     weight: np.ndarray = None  # (..., K, 1)
     complex_bingham: ComplexBingham = None
-
-    def _model(self, indep, K, D, device):
-        t = _lib.torch()
-        V = _lib.to_device(self.complex_bingham.covariance_eigenvectors, t.complex128).to(device)
-        lam = _lib.to_device(self.complex_bingham.covariance_eigenvalues, t.float64).to(device)
-        return (V.expand(*indep, K, D, D).reshape(-1, K, D, D).contiguous(),
-                lam.expand(*indep, K, D).reshape(-1, K, D).contiguous())
 
     def predict(self, y, affiliation_eps=0):
         """y (..., N, D) -> affiliations (..., K, N) (reference :25-40; the observation is
@@ -66,23 +55,23 @@ class CBMM(_ProbabilisticModel):
         assert y.dtype in (t.complex64, t.complex128), y.dtype
         *indep, N, D = y.shape
         indep = tuple(indep)
-        K = self.complex_bingham.covariance_eigenvalues.shape[-2]
+        cb = self.complex_bingham
+        K = cb.covariance_eigenvalues.shape[-2]
         _check_shape(D, K)
-        V, lam = self._model(indep, K, D, y.device)
+        V = mix.flatten_param(cb.covariance_eigenvectors, indep, (K, D, D), t.complex128, y.device)
+        lam = mix.flatten_param(cb.covariance_eigenvalues, indep, (K, D), t.float64, y.device)
         B = V.shape[0]
         yb = y.reshape(-1, N, D).contiguous()
         w = _lib.to_device(self.weight, t.float64).to(y.device)
         if w.shape[-1] == 1 and affiliation_eps == 0:
-            wb = w.expand(*indep, K, 1).reshape(B, K).contiguous()
+            wb = mix.flatten_param(w, indep, (K, 1), t.float64).reshape(B, K)
             r = engine.cbmm_fit(yb, K, model=(V, lam, wb), iterations=0, final_predict=True)
             return as_result(r['affiliation'].reshape(*indep, K, N), like_torch)
         # frame-varying weights or a clipped softmax (reference :42-58): class log-pdfs, then the
         # general softmax step
-        r = engine.cbmm_fit(yb, K, model=(V, lam, t.ones((B, K), dtype=t.float64,
-                                                          device=y.device)),
-                            iterations=0, want_log_pdf=True)
-        aff = engine.log_pdf_to_affiliation(r['log_pdf'], _broadcast_weight(w, indep,
-                                                                            len(indep) + 2),
+        ones_w = t.ones((B, K), dtype=t.float64, device=y.device)
+        aff = engine.log_pdf_to_affiliation(_log_pdf(yb, K, V, lam, ones_w),
+                                            mix.flatten_weight(w, indep),
                                             affiliation_eps=affiliation_eps)
         return as_result(aff.reshape(*indep, K, N), like_torch)
 
@@ -106,104 +95,45 @@ class CBMMTrainer:
             inline_permutation_aligner=None) -> CBMM:
         """EM for complex-Bingham mixtures, any number of independent axes
         (reference :79-167).  y (..., T, D); initialization (..., K, T)."""
-        assert xor(initialization is None, num_classes is None), (
-            "Incompatible input combination. "
-            "Exactly one of the two inputs has to be None: "
-            f"{initialization is None} xor {num_classes is None}"
-        )
-        like_torch = _lib.is_torch(y)
+        p = mix.prepare_fit(y, initialization, num_classes, saliency, weight_constant_axis,
+                            complex_input=True)
+        indep, N, D, K, like_torch = p.indep, p.N, p.D, p.K, p.like_torch
         t = _lib.torch()
-        y = _lib.to_device(y)
-        assert y.dtype in (t.complex64, t.complex128), y.dtype
-        assert y.shape[-1] > 1
-        *indep, N, D = y.shape
-        indep = tuple(indep)
-        if initialization is None:
-            gamma0 = random_affiliation((*indep, num_classes, N), y.device)  # global NumPy RNG
-        else:
-            gamma0 = _lib.to_device(initialization, t.float64).to(y.device)
-            num_classes = gamma0.shape[-2]
-            gamma0 = gamma0.expand(*indep, num_classes, N)
-        K = num_classes
-        if self.dimension is None:
-            self.dimension = D
-        else:
-            assert self.dimension == D, (
-                'You initialized the trainer with a different dimension than '
-                'you are using to fit a model. Use a new trainer, when you '
-                'change the dimension.')
+        mix.check_dimension(self, D)
         _check_shape(D, K)
-        if isinstance(weight_constant_axis, list):
-            weight_constant_axis = tuple(weight_constant_axis)
+        yb = p.y.reshape(-1, N, D).contiguous()
+        B = yb.shape[0]
         # the reference always passes a saliency, ones by default (:148-149)
-        if saliency is None:
-            sal = t.ones((*indep, N), dtype=t.float64, device=y.device)
-        else:
-            sal = _lib.to_device(saliency, t.float64).to(y.device).expand(*indep, N)
-        sal = sal.reshape(-1, N).contiguous()
-        yb = y.reshape(-1, N, D).contiguous()
-        mode = CACGMMTrainer._weight_mode(weight_constant_axis, len(indep) + 2)
+        sal = p.saliency
+        if sal is None:
+            sal = t.ones((B, N), dtype=t.float64, device=yb.device)
+        options = dict(max_concentration=self.max_concentration, eigenvalue_eps=self.eigenvalue_eps)
+        mode = mix.fused_weight_mode(p.weight_constant_axis, p.ndim)
         if mode is not None and inline_permutation_aligner is None and affiliation_eps == 0:
-            r = engine.cbmm_fit(yb, K, gamma0=gamma0.reshape(-1, K, N).contiguous(),
-                                iterations=iterations, saliency=sal, weight_mode=mode,
-                                max_concentration=self.max_concentration,
-                                eigenvalue_eps=self.eigenvalue_eps)
-            if mode == _lib.WEIGHT_UNIFORM:
-                weight = t.full((K, 1), 1.0 / K, dtype=t.float64, device=yb.device)
-            else:
-                weight = r['weight'].reshape(*indep, K, 1)
-            return self._model(weight, r, indep, K, D, like_torch)
-        return self._fit_stepwise(yb, indep, K, gamma0, iterations, sal, weight_constant_axis,
-                                  affiliation_eps, inline_permutation_aligner, like_torch)
+            r = engine.cbmm_fit(yb, K, gamma0=p.gamma0.reshape(-1, K, N).contiguous(),
+                                iterations=iterations, saliency=sal, weight_mode=mode, **options)
+            V, lam = r['eigvec'], r['eigval']
+            weight = mix.fused_weight(mode, r['weight'], indep, K, yb.device)
+        else:
+            # The reference loop (:181-203) for the options the fused kernel does not take
+            # (weights shared over independent axes or frame-varying, an inline aligner, a
+            # clipped softmax): `pbbss_cbmm_fit` with iterations = 0 (class log-pdfs) and
+            # iterations = 1 (M-step) around the shared softmax / aligner / weight steps
+            ones_w = t.ones((B, K), dtype=t.float64, device=yb.device)
 
-    @staticmethod
-    def _model(weight, r, indep, K, D, like_torch):
+            def m_step(masked):
+                r = engine.cbmm_fit(yb, K, gamma0=masked, iterations=1, **options)
+                return r['eigvec'], r['eigval']
+
+            (V, lam), weight = mix.stepwise_em(
+                p.gamma0, iterations, lambda model: _log_pdf(yb, K, *model, ones_w), m_step,
+                saliency=sal, weight_constant_axis=p.weight_constant_axis,
+                aligner=inline_permutation_aligner, affiliation_eps=affiliation_eps)
         return CBMM(
             weight=as_result(weight, like_torch),
             complex_bingham=ComplexBingham(
-                covariance_eigenvectors=as_result(r['eigvec'].reshape(*indep, K, D, D),
-                                                  like_torch),
-                covariance_eigenvalues=as_result(r['eigval'].reshape(*indep, K, D), like_torch)))
-
-    def _fit_stepwise(self, yb, indep, K, gamma0, iterations, sal, weight_constant_axis,
-                      affiliation_eps, aligner, like_torch):
-        """The reference loop (:181-203) for the options the fused kernel does not take
-        (weights shared over independent axes or frame-varying, an inline aligner, a clipped
-        softmax), every step a device kernel: class log-pdfs (`pbbss_cbmm_fit`, iterations = 0),
-        the softmax with the reference-shaped weight (`pbbss_log_pdf_to_affiliation`), the weight
-        reduction (`pbbss_estimate_mixture_weight`) and the M-step (`pbbss_cbmm_fit`,
-        iterations = 1)."""
-        from . import _embed_stepwise as sw
-        t = _lib.torch()
-        B, N, D = yb.shape
-        shape = (*indep, K, N)
-        aff = gamma0.reshape(shape).contiguous()
-        sal_dev = sal.reshape(*indep, N)
-        ones_w = t.ones((B, K), dtype=t.float64, device=yb.device)
-        r = weight = None
-        for _ in range(iterations):
-            if r is not None:
-                lp = engine.cbmm_fit(yb, K, model=(r['eigvec'], r['eigval'], ones_w),
-                                     iterations=0, want_log_pdf=True)['log_pdf']
-                aff = engine.log_pdf_to_affiliation(
-                    lp, _broadcast_weight(weight, indep, len(shape)),
-                    affiliation_eps=affiliation_eps).reshape(shape)
-                if aligner is not None:
-                    if type(aligner).__module__.startswith('pb_bss_amd'):
-                        aff = apply_inline_permutation_alignment(
-                            affiliation=aff, weight_constant_axis=weight_constant_axis,
-                            aligner=aligner).contiguous()
-                    else:  # a foreign (NumPy) aligner object: the one host excursion left
-                        aff = _lib.to_device(apply_inline_permutation_alignment(
-                            affiliation=_lib.to_host(aff),
-                            weight_constant_axis=weight_constant_axis, aligner=aligner),
-                            t.float64).to(yb.device).contiguous()
-            weight = sw.device_weight(aff, sal_dev, weight_constant_axis, indep)
-            masked = aff * sal_dev[..., None, :]
-            r = engine.cbmm_fit(yb, K, gamma0=masked.reshape(B, K, N).contiguous(),
-                                iterations=1, max_concentration=self.max_concentration,
-                                eigenvalue_eps=self.eigenvalue_eps)
-        return self._model(weight, r, indep, K, D, like_torch)
+                covariance_eigenvectors=as_result(V.reshape(*indep, K, D, D), like_torch),
+                covariance_eigenvalues=as_result(lam.reshape(*indep, K, D), like_torch)))
 
     def fit_predict(self, y, initialization=None, num_classes=None, iterations=100, *,
                     saliency=None, weight_constant_axis=(-1,), affiliation_eps=0,

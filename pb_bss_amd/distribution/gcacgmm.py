@@ -7,13 +7,11 @@ default, csrc/embed.hip), 'diagonal' (as the reference writes its log-pdf) and '
 (csrc/gauss_full.hip on the FP64 matrix pipe).
 """
 from dataclasses import dataclass
-from operator import xor
 from typing import Any
-
-import numpy as np
 
 from .. import _lib
 from . import _joint
+from ._mixture import check_one_of
 from .complex_angular_central_gaussian import ComplexAngularCentralGaussian
 from .gaussian import DiagonalGaussian, Gaussian, SphericalGaussian
 from .utils import _ProbabilisticModel, as_result
@@ -63,11 +61,7 @@ class GCACGMMTrainer:
             weight_constant_axis=(-1,), spatial_weight=1., spectral_weight=1.,
             inline_permutation_alignment=False) -> GCACGMM:
         """(:131-246).  initialization (F, K, T); saliency (F, T)."""
-        assert xor(initialization is None, num_classes is None), (
-            "Incompatible input combination. "
-            "Exactly one of the two inputs has to be None: "
-            f"{initialization is None} xor {num_classes is None}"
-        )
+        check_one_of(initialization, num_classes)
         if covariance_type not in _KIND:
             raise ValueError(f"Unknown covariance type '{covariance_type}'.")  # gaussian.py:184
         r, like_torch = _joint.fit(

@@ -10,13 +10,14 @@ single-Gaussian fit kernels, no host round trip inside the loop).  BinaryGMM wra
 KMeans and is out of scope.
 """
 from dataclasses import dataclass
-from operator import xor
 
 import numpy as np
 
 from .. import _lib, engine
+from . import _embed_stepwise as sw
+from . import _mixture as mix
 from .gaussian import DiagonalGaussian, Gaussian, SphericalGaussian
-from .utils import _ProbabilisticModel, as_result, random_affiliation
+from .utils import _ProbabilisticModel, as_result
 from ..utils import labels_to_one_hot  # noqa: F401  (names the reference module exposes)
 from .gaussian import GaussianTrainer  # noqa: F401  (names the reference module exposes)
 from .mixture_model_utils import estimate_mixture_weight, log_pdf_to_affiliation  # noqa: F401  (names the reference module exposes)
@@ -24,7 +25,7 @@ from .mixture_model_utils import estimate_mixture_weight, log_pdf_to_affiliation
 __all__ = ['GMM', 'GMMTrainer']
 
 
-_CLASS, _UNIFORM, _ONES = range(3)
+_CLASS, _UNIFORM, _ONES = _lib.WEIGHT_PER_CLASS_MEAN, _lib.WEIGHT_UNIFORM, mix.WEIGHT_ONES
 
 
 def _weight_kind(weight_constant_axis, ndim):
@@ -32,20 +33,9 @@ def _weight_kind(weight_constant_axis, ndim):
     (-1,) / -1: per-class weights (K, 1); int -2: the constant 1/K (:180-183);
     tuple (-2,) -- the default of fit_predict --: the general path averages over the class
     axis and L1-normalises along it, i.e. a (1, N) array of ones (:192-201).  Weights that
-    are constant over the classes cancel in the posterior, so both run as the uniform mode."""
-    axis = weight_constant_axis
-    if isinstance(axis, list):
-        axis = tuple(axis)
-    if isinstance(axis, int):
-        if axis % ndim - ndim == -2:
-            return _UNIFORM
-        axis = (axis,)
-    norm = tuple(a % ndim - ndim for a in axis)
-    if norm == (-1,):
-        return _CLASS
-    if norm == (-2,):
-        return _ONES
-    return None  # any other axis set: the step-wise device loop (_embed_stepwise.py)
+    are constant over the classes cancel in the posterior, so both run as the uniform mode.
+    None: any other axis set, the step-wise device loop (_embed_stepwise.py)."""
+    return mix.fused_weight_mode(weight_constant_axis, ndim, ones=True)
 
 
 def _check_covariance_type(covariance_type):
@@ -75,40 +65,32 @@ class GMM(_ProbabilisticModel):
         x = _lib.to_device(x)
         assert not x.is_complex(), x.dtype
         *indep, N, E = x.shape
-        mean = _lib.to_device(self.gaussian.mean, t.float64).to(x.device)
-        K = mean.shape[-2]
-        cov = _lib.to_device(self.gaussian.covariance, t.float64).to(x.device)
+        K = self.gaussian.mean.shape[-2]
         kind = _kind_of(self.gaussian)
         full = kind == 'full'
+        cs = mix.covariance_shape(kind, E)
+        mean = mix.flatten_param(self.gaussian.mean, indep, (K, E), t.float64, x.device)
+        cov = mix.flatten_param(self.gaussian.covariance, indep, (K, *cs), t.float64, x.device)
         w = _lib.to_device(self.weight, t.float64).to(x.device)
         general = kind == 'diagonal' or (w.shape[-1] != 1 and w.shape[-2] != 1) or (
             w.ndim > 2 and any(a != 1 for a in w.shape[:-2]) and w.shape[-1] != 1)
         if general:
             # diagonal covariances / weights that vary over classes AND frames: the general
             # log-pdf + softmax steps
-            from . import _embed_stepwise as sw
-            cs = {'full': (E, E), 'diagonal': (E,), 'spherical': ()}[kind]
-            aff = sw.affiliation(
-                kind, x.reshape(-1, N, E), mean.expand(*indep, K, E).reshape(-1, K, E).contiguous(),
-                cov.expand(*indep, K, *cs).reshape(-1, K, *cs).contiguous(), w, tuple(indep), K, N)
+            aff = sw.affiliation(kind, x.reshape(-1, N, E), mean, cov, w, tuple(indep))
             return as_result(aff.reshape(*indep, K, N), like_torch)
         if w.shape[-1] != 1:
             # (..., 1, N): constant over the classes (weight_constant_axis=(-2,)), cancels in
             # the posterior (mixture_model_utils.py:37-47) -- evaluated with uniform weights
             if w.shape[-2] != 1:
                 raise NotImplementedError(f'frame-dependent class weights {tuple(w.shape)}')
-            w = t.full((K, 1), 1.0 / K, dtype=t.float64, device=x.device)
-        cshape = (E, E) if full else ()
-        model = (mean.expand(*indep, K, E).reshape(-1, K, E).contiguous(),
-                 cov.expand(*indep, K, *cshape).reshape(-1, K, *cshape).contiguous(),
-                 w.expand(*indep, K, 1).reshape(-1, K).contiguous())
+            w = mix.uniform_weight(K, x.device)
+        model = (mean, cov, mix.flatten_param(w, indep, (K, 1), t.float64).reshape(-1, K))
         if full:
             r = engine.gmm_full_fit(x.reshape(-1, N, E), K, model=model, iterations=0,
                                     final_predict=True)
             if int(r['status'].item()) != 0:
-                raise ValueError(  # sklearn's _compute_precision_cholesky (gaussian.py:26)
-                    'Fitting the mixture model failed because some components have ill-defined empirical '
-                'covariance (not positive definite)')
+                raise mix.not_positive_definite()
         else:
             r = engine.gmm_fit(x.reshape(-1, N, E), K, model=model, iterations=0,
                                final_predict=True)
@@ -124,81 +106,52 @@ class GMMTrainer:
             weight_constant_axis=(-1,), covariance_type='full', fixed_covariance=None):
         """y (..., N, D) real; initialization (..., K, N); saliency (..., N);
         fixed_covariance (..., K) (:33-95)."""
-        assert xor(initialization is None, num_classes is None), (
-            "Incompatible input combination. "
-            "Exactly one of the two inputs has to be None: "
-            f"{initialization is None} xor {num_classes is None}"
-        )
         _check_covariance_type(covariance_type)
-        like_torch = _lib.is_torch(y)
+        p = mix.prepare_fit(y, initialization, num_classes, saliency, weight_constant_axis,
+                            complex_input=False)
+        y, indep, N, E, K, like_torch = p.y, p.indep, p.N, p.D, p.K, p.like_torch
         t = _lib.torch()
-        y = _lib.to_device(y)
-        assert not y.is_complex(), y.dtype
-        *indep, N, E = y.shape
-        indep = tuple(indep)
-        if initialization is None:
-            # global NumPy RNG (:72-77)
-            gamma0 = random_affiliation((*indep, num_classes, N), y.device)
-        else:
-            gamma0 = _lib.to_device(initialization, t.float64).to(y.device)
-            num_classes = gamma0.shape[-2]
-            gamma0 = gamma0.expand(*indep, num_classes, N)
-        K = num_classes
-        kind = _weight_kind(weight_constant_axis, len(indep) + 2)
-        if kind is None or covariance_type == 'diagonal':
-            if iterations <= 0:
-                return None
-            from . import _embed_stepwise as sw
-            cs = {'full': (E, E), 'diagonal': (E,), 'spherical': ()}[covariance_type]
-            fixed = None
-            if fixed_covariance is not None:
-                fixed = _lib.to_device(fixed_covariance, t.float64).to(y.device)
-                assert tuple(fixed.shape) == (*indep, K, *cs), (
-                    f'{tuple(fixed.shape)} != {(*indep, K, *cs)}')  # :161-163
-            r = sw.fit(covariance_type, y, gamma0.contiguous(), iterations, saliency,
-                       weight_constant_axis, fixed_scale=fixed)
-            return GMM(
-                weight=as_result(r['weight'], like_torch),
-                gaussian=_CLS[covariance_type](
-                    mean=as_result(r['mean'].reshape(*indep, K, E), like_torch),
-                    covariance=as_result(r['scale'].reshape(*indep, K, *cs), like_torch)))
-        mode = _lib.WEIGHT_PER_CLASS_MEAN if kind == _CLASS else _lib.WEIGHT_UNIFORM
-        sal = None
-        if saliency is not None:  # None: ones (:79-80), which the kernels assume anyway
-            sal = _lib.to_device(saliency, t.float64).to(y.device).expand(*indep, N)
-            sal = sal.reshape(-1, N).contiguous()
-            if kind == _ONES and not bool((sal > 0).all().item()):
-                raise NotImplementedError(
-                    'weight_constant_axis=(-2,) with zero saliency entries (zero weights)')
+        kind = _weight_kind(p.weight_constant_axis, p.ndim)
+        # the fused loops serve 'spherical' and 'full' with the class-wise / uniform weights
+        stepwise = kind is None or covariance_type == 'diagonal'
         full = covariance_type == 'full'
-        cshape = (E, E) if full else ()
+        cs = mix.covariance_shape(covariance_type, E)
+        sal = p.saliency  # None: ones (:79-80), which the kernels assume anyway
+        if sal is not None and not stepwise and kind == _ONES \
+                and not bool((sal > 0).all().item()):
+            raise NotImplementedError(
+                'weight_constant_axis=(-2,) with zero saliency entries (zero weights)')
         fixed = None
         if fixed_covariance is not None:
             fixed = _lib.to_device(fixed_covariance, t.float64).to(y.device)
-            assert tuple(fixed.shape) == (*indep, K, *cshape), (
-                f'{tuple(fixed.shape)} != {(*indep, K, *cshape)}')  # :161-163
-            fixed = fixed.reshape(-1, K, *cshape).contiguous()
+            assert tuple(fixed.shape) == (*indep, K, *cs), (
+                f'{tuple(fixed.shape)} != {(*indep, K, *cs)}')  # :161-163
         if iterations <= 0:
             return None  # the reference's loop body never runs (:127-141)
-        fit = engine.gmm_full_fit if full else engine.gmm_fit
-        r = fit(y.reshape(-1, N, E), K, gamma0=gamma0.reshape(-1, K, N).contiguous(),
-                iterations=iterations, saliency=sal, weight_mode=mode, fixed_covariance=fixed)
-        if full and int(r['status'].item()) != 0:
-            raise ValueError(  # sklearn's _compute_precision_cholesky (gaussian.py:26)
-                'Fitting the mixture model failed because some components have ill-defined empirical '
-                'covariance (not positive definite)')
-        if kind == _UNIFORM:
-            weight = t.full((K, 1), 1.0 / K, dtype=t.float64, device=y.device)
-        elif kind == _ONES:
-            weight = t.ones((*indep, 1, N), dtype=t.float64, device=y.device)
+        if stepwise:
+            r = sw.fit(covariance_type, y, p.gamma0, iterations, sal, p.weight_constant_axis,
+                       fixed_scale=fixed)
+            weight, cov = r['weight'], r['scale']
         else:
-            weight = r['weight'].reshape(*indep, K, 1)
-        cls = Gaussian if full else SphericalGaussian
+            if fixed is not None:
+                fixed = fixed.reshape(-1, K, *cs).contiguous()
+            fit = engine.gmm_full_fit if full else engine.gmm_fit
+            r = fit(y.reshape(-1, N, E), K, gamma0=p.gamma0.reshape(-1, K, N).contiguous(),
+                    iterations=iterations, saliency=sal,
+                    weight_mode=_lib.WEIGHT_PER_CLASS_MEAN if kind == _CLASS
+                    else _lib.WEIGHT_UNIFORM, fixed_covariance=fixed)
+            if full and int(r['status'].item()) != 0:
+                raise mix.not_positive_definite()
+            if kind == _ONES:
+                weight = t.ones((*indep, 1, N), dtype=t.float64, device=y.device)
+            else:
+                weight = mix.fused_weight(kind, r['weight'], indep, K, y.device)
+            cov = r['covariance']
         return GMM(
             weight=as_result(weight, like_torch),
-            gaussian=cls(
+            gaussian=_CLS[covariance_type](
                 mean=as_result(r['mean'].reshape(*indep, K, E), like_torch),
-                covariance=as_result(r['covariance'].reshape(*indep, K, *cshape), like_torch)))
+                covariance=as_result(cov.reshape(*indep, K, *cs), like_torch)))
 
     def fit_predict(self, y, initialization=None, num_classes=None, iterations=100, *,
                     saliency=None, weight_constant_axis=(-2,), covariance_type='full',

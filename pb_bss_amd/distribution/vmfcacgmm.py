@@ -6,11 +6,11 @@ As in the reference, the M-step sees the embedding as given (vmfcacgmm.py:267-27
 while the vMF log-pdf unit-normalises it (von_mises_fisher.py:71-73).
 """
 from dataclasses import dataclass
-from operator import xor
 from typing import Any
 
 from .. import _lib
 from . import _joint
+from ._mixture import check_one_of
 from .complex_angular_central_gaussian import ComplexAngularCentralGaussian
 from .utils import _ProbabilisticModel, as_result
 from .von_mises_fisher import VonMisesFisher
@@ -47,11 +47,7 @@ class VMFCACGMMTrainer:
             weight_constant_axis=(-1,), spatial_weight=1., spectral_weight=1.,
             inline_permutation_alignment=False) -> VMFCACGMM:
         """(:101-205)."""
-        assert xor(initialization is None, num_classes is None), (
-            "Incompatible input combination. "
-            "Exactly one of the two inputs has to be None: "
-            f"{initialization is None} xor {num_classes is None}"
-        )
+        check_one_of(initialization, num_classes)
         r, like_torch = _joint.fit(
             _lib.EMBED_VMF, observation, embedding, initialization, num_classes, iterations,
             saliency, covariance_norm=covariance_norm, eigenvalue_floor=eigenvalue_floor,

@@ -7,31 +7,18 @@ E-step kernel over the transposed embedding and one M-step reduction over the
 row-major embedding, enqueued back to back on the caller's stream.
 """
 from dataclasses import dataclass
-from operator import xor
 
 import numpy as np
 
 from .. import _lib, engine
-from .utils import _ProbabilisticModel, as_result, random_affiliation
+from . import _embed_stepwise as sw
+from . import _mixture as mix
+from .utils import _ProbabilisticModel, as_result
 from .von_mises_fisher import VonMisesFisher
 from .von_mises_fisher import VonMisesFisherTrainer  # noqa: F401  (names the reference module exposes)
 from .mixture_model_utils import estimate_mixture_weight, log_pdf_to_affiliation  # noqa: F401  (names the reference module exposes)
 
 __all__ = ['VMFMM', 'VMFMMTrainer']
-
-
-def _weight_mode(weight_constant_axis, ndim):
-    """(-1,) / -1 -> per-mixture class weights; int -2 -> uniform 1/K (the only
-    spelling the reference's estimate_mixture_weight maps to 1/K)."""
-    if isinstance(weight_constant_axis, list):
-        weight_constant_axis = tuple(weight_constant_axis)
-    if isinstance(weight_constant_axis, int):
-        if weight_constant_axis % ndim - ndim == -2:
-            return _lib.WEIGHT_UNIFORM
-        weight_constant_axis = (weight_constant_axis,)
-    if tuple(a % ndim - ndim for a in weight_constant_axis) == (-1,):
-        return _lib.WEIGHT_PER_CLASS_MEAN
-    return None  # any other axis set: the step-wise device loop (_embed_stepwise.py)
 
 
 @dataclass
@@ -46,21 +33,16 @@ class VMFMM(_ProbabilisticModel):
         y = _lib.to_device(y)
         assert not y.is_complex(), y.dtype
         *indep, N, E = y.shape
-        mean = _lib.to_device(self.vmf.mean, t.float64).to(y.device)
-        K = mean.shape[-2]
-        conc = _lib.to_device(self.vmf.concentration, t.float64).to(y.device)
+        K = self.vmf.mean.shape[-2]
+        mean = mix.flatten_param(self.vmf.mean, indep, (K, E), t.float64, y.device)
+        conc = mix.flatten_param(self.vmf.concentration, indep, (K,), t.float64, y.device)
         w = _lib.to_device(self.weight, t.float64).to(y.device)
         if w.shape[-1] != 1 or (w.ndim > 2 and tuple(w.shape[:-2]) != tuple(indep)
                                 and any(a != 1 for a in w.shape[:-2])):
             # frame-varying weights (weight_constant_axis without -1): the general softmax step
-            from . import _embed_stepwise as sw
-            aff = sw.affiliation(
-                'vmf', y.reshape(-1, N, E), mean.expand(*indep, K, E).reshape(-1, K, E).contiguous(),
-                conc.expand(*indep, K).reshape(-1, K).contiguous(), w, tuple(indep), K, N)
+            aff = sw.affiliation('vmf', y.reshape(-1, N, E), mean, conc, w, tuple(indep))
             return as_result(aff.reshape(*indep, K, N), like_torch)
-        model = (mean.expand(*indep, K, E).reshape(-1, K, E).contiguous(),
-                 conc.expand(*indep, K).reshape(-1, K).contiguous(),
-                 w.expand(*indep, K, 1).reshape(-1, K).contiguous())
+        model = (mean, conc, mix.flatten_param(w, indep, (K, 1), t.float64).reshape(-1, K))
         r = engine.vmfmm_fit(y.reshape(-1, N, E), K, model=model, iterations=0,
                              final_predict=True)
         return as_result(r['affiliation'].reshape(*indep, K, N), like_torch)
@@ -75,53 +57,29 @@ class VMFMMTrainer:
             weight_constant_axis=(-1,), min_concentration=1e-10, max_concentration=500):
         """EM for vMFMMs with any number of independent dimensions (:42-104).
         y (..., N, D) real; initialization (..., K, N); saliency (..., N)."""
-        assert xor(initialization is None, num_classes is None), (
-            "Incompatible input combination. "
-            "Exactly one of the two inputs has to be None: "
-            f"{initialization is None} xor {num_classes is None}"
-        )
-        like_torch = _lib.is_torch(y)
-        t = _lib.torch()
-        y = _lib.to_device(y)
-        assert not y.is_complex(), y.dtype
-        *indep, N, E = y.shape
-        indep = tuple(indep)
-        if initialization is None:
-            # global NumPy RNG (:83-86)
-            gamma0 = random_affiliation((*indep, num_classes, N), y.device)
-        else:
-            gamma0 = _lib.to_device(initialization, t.float64).to(y.device)
-            num_classes = gamma0.shape[-2]
-            gamma0 = gamma0.expand(*indep, num_classes, N)
-        K = num_classes
+        p = mix.prepare_fit(y, initialization, num_classes, saliency, weight_constant_axis,
+                            complex_input=False)
+        y, indep, N, E, K, like_torch = p.y, p.indep, p.N, p.D, p.K, p.like_torch
         assert iterations > 0, iterations
-        mode = _weight_mode(weight_constant_axis, len(indep) + 2)
+        # any axis set but (-1,) / -1 / int -2: the step-wise device loop (_embed_stepwise.py)
+        mode = mix.fused_weight_mode(p.weight_constant_axis, p.ndim)
         if mode is None:
-            from . import _embed_stepwise as sw
-            r = sw.fit('vmf', y, gamma0.contiguous(), iterations, saliency, weight_constant_axis,
+            r = sw.fit('vmf', y, p.gamma0, iterations, p.saliency, p.weight_constant_axis,
                        min_concentration=min_concentration, max_concentration=max_concentration)
-            return VMFMM(
-                weight=as_result(r['weight'], like_torch),
-                vmf=VonMisesFisher(
-                    mean=as_result(r['mean'].reshape(*indep, K, E), like_torch),
-                    concentration=as_result(r['scale'].reshape(*indep, K), like_torch)))
-        sal = None
-        if saliency is not None:
-            sal = _lib.to_device(saliency, t.float64).to(y.device).expand(*indep, N)
-            sal = sal.reshape(-1, N).contiguous()
-        r = engine.vmfmm_fit(y.reshape(-1, N, E), K, gamma0=gamma0.reshape(-1, K, N).contiguous(),
-                             iterations=iterations, saliency=sal, weight_mode=mode,
-                             min_concentration=min_concentration,
-                             max_concentration=max_concentration)
-        if mode == _lib.WEIGHT_UNIFORM:
-            weight = t.full((K, 1), 1.0 / K, dtype=t.float64, device=y.device)
+            weight, conc = r['weight'], r['scale']
         else:
-            weight = r['weight'].reshape(*indep, K, 1)
+            r = engine.vmfmm_fit(y.reshape(-1, N, E), K,
+                                 gamma0=p.gamma0.reshape(-1, K, N).contiguous(),
+                                 iterations=iterations, saliency=p.saliency, weight_mode=mode,
+                                 min_concentration=min_concentration,
+                                 max_concentration=max_concentration)
+            weight = mix.fused_weight(mode, r['weight'], indep, K, y.device)
+            conc = r['concentration']
         return VMFMM(
             weight=as_result(weight, like_torch),
             vmf=VonMisesFisher(
                 mean=as_result(r['mean'].reshape(*indep, K, E), like_torch),
-                concentration=as_result(r['concentration'].reshape(*indep, K), like_torch)))
+                concentration=as_result(conc.reshape(*indep, K), like_torch)))
 
     def fit_predict(self, y, initialization=None, num_classes=None, iterations=100,
                     saliency=None, weight_constant_axis=(-1,), min_concentration=1e-10,

@@ -82,6 +82,25 @@ def _checked_with_split_retry(launch, dev, what):
     return r
 
 
+def _cooperative_timed_out(status, dev):
+    """True when a cooperative shared-weight launch did not get its workgroups co-resident (other
+    kernels of this process held the compute units): some status words carry the time-out pattern
+    -- .any(): the groups of a big batch go out as several cooperative launches, one of which can
+    time out alone -- and the handle's wait flag is up.  Not a numerical failure: the report is
+    consumed (see _checked_with_split_retry), the caller of the engine function is warned and the
+    function answers "not served", so that the step-wise loop, which needs no co-residency, runs."""
+    # the status test first: split_error() is a blocking read of the handle's flag word and is
+    # only worth its round trip when some status word carries the time-out pattern
+    if not (bool(((status & _SPLIT_POISON) == _SPLIT_POISON).any().item())
+            and split_error(dev.index)):
+        return False
+    import warnings
+    warnings.warn('cooperative shared-weight launch timed out waiting for co-residency; '
+                  'repeating the fit step by step', RuntimeWarning, stacklevel=3)
+    split_reset(dev.index)
+    return True
+
+
 def normalize_observation(y):
     """pbbss_normalize_observation: (B,T,D) complex -> (B,D,T), unit norm."""
     t = _t()
@@ -211,20 +230,7 @@ def em_fit_shared(y, K, group, *, weight_mode, gamma0=None, model=None, iteratio
         return None
     _lib.check(rc, f'cacgmm_fit_shared(B={B},group={group},T={T},D={D},K={K})')
     if check_status:
-        poison = _lib.ST_NONFINITE | _lib.ST_EIG_NOCONV
-        # the status test first: split_error() is a blocking read of the handle's flag word and
-        # is only worth its round trip when some status word carries the time-out pattern
-        if iterations > 0 and bool(((out_st & poison) == poison).any().item()) \
-                and split_error(dev.index):
-            # some status words carry the time-out pattern and the handle's wait flag is up (the
-            # groups of a big batch go out as several cooperative launches: one of them can time
-            # out alone): a cooperative launch did not get its workgroups co-resident (other
-            # kernels of this process held the compute units).  Not a numerical failure: say "not served"
-            # and let the caller run the step-wise loop, which needs no co-residency.
-            import warnings
-            warnings.warn('cooperative shared-weight launch timed out waiting for co-residency; '
-                          'repeating the fit step by step', RuntimeWarning, stacklevel=2)
-            split_reset(dev.index)  # consume the report (see _checked_with_split_retry)
+        if iterations > 0 and _cooperative_timed_out(out_st, dev):
             return None
         _status_raise_em(out_st, 'CACGMMTrainer.fit')
     return dict(eigvec=out_vec, eigval=out_val, weight=out_w, status=out_st,
@@ -609,15 +615,7 @@ def cwmm_fit(y, K, spline, *, gamma0=None, model=None, iterations=100, saliency=
         if r is None:
             return None
         if check_status:
-            poison = _lib.ST_NONFINITE | _lib.ST_EIG_NOCONV
-            # .any(): the groups of a big batch go out as several cooperative launches, one of
-            # which can time out alone
-            if bool(((r['status'] & poison) == poison).any().item()) and split_error(dev.index):
-                import warnings
-                warnings.warn('cooperative shared-weight launch timed out waiting for '
-                              'co-residency; repeating the fit step by step', RuntimeWarning,
-                              stacklevel=2)
-                split_reset(dev.index)
+            if _cooperative_timed_out(r['status'], dev):
                 return None
             _status_raise_em(r['status'], 'CWMMTrainer.fit')
         return r
@@ -1023,12 +1021,7 @@ def log_pdf_to_affiliation(log_pdf, weight, activity=None, affiliation_eps=0.):
     it -- (B,K,1), (K,1), (1,K,N), (B,1,N) ...: singleton axes become zero strides -> (B,K,N)."""
     t = _t()
     B, K, N = log_pdf.shape
-    w = weight.to(t.float64)
-    while w.ndim < 3:
-        w = w.unsqueeze(0)
-    assert w.ndim == 3 and all(a in (1, b) for a, b in zip(w.shape, (B, K, N))), (w.shape, (B, K, N))
-    w = w.contiguous()
-    st = [0 if w.shape[i] == 1 else w.stride(i) for i in range(3)]
+    w, st = _broadcast_weight(weight, (B, K, N))
     out = t.empty((B, K, N), dtype=t.float64, device=log_pdf.device)
     if activity is not None:
         assert activity.shape == (B, K, N) and activity.dtype == t.uint8
