@@ -33,7 +33,8 @@ extern "C" {
 
 #define PBBSS_VERSION 610 /* still 0.6.1 (the value is pinned by the symbol test): pbbss_cbmm_fit,
                              pbbss_cbingham_find_eigenvalues, PBBSS_ST_SOLVE_NOCONV,
-                             pbbss_deflation_seed added since;
+                             pbbss_deflation_seed, pbbss_mask_pointwise, pbbss_mask_lorenz,
+                             pbbss_mask_quantile added since;
                              0.6.1: pbbss_select_reference_channel, pbbss_apply_beamforming_vector_shared;
                              0.6.0: pbbss_log_pdf_to_affiliation_inline_pa, D = 33 / 34 in pbbss_cacgmm_fit / _predict;
                              0.4.1: pbbss_set_dhtv_probe; 0.4.0: pbbss_split_reset, pbbss_set_spin_limit, pbbss_reference_channel_terms,
@@ -87,7 +88,9 @@ int pbbss_create(pbbss_handle_t* out, int device_id);
  * (pbbss_vmfmm_fit, pbbss_gmm_fit, pbbss_embed_fit, pbbss_embed_log_pdf): 1 <= K <= 64,
  * 1 <= E <= 256.  LCMV: D <= 8.  Deflation seed
  * (pbbss_deflation_seed): fused for D <= 8, three launches per round around the generic
- * eigensolver for 9 <= D <= 32; 2 <= K <= 19; any T > 2 neighbors. */
+ * eigensolver for 9 <= D <= 32; 2 <= K <= 19; any T > 2 neighbors.  Oracle masks
+ * (pbbss_mask_pointwise, pbbss_mask_lorenz, pbbss_mask_quantile): 1 <= K <= 9 sources,
+ * 1 <= D <= 34 pooled sensors, up to 8 quantiles per call, rows of any length. */
 int pbbss_destroy(pbbss_handle_t h);
 
 /* ------------------------------------------------------------------------- */
@@ -555,6 +558,82 @@ int pbbss_deflation_seed(pbbss_handle_t h, const void* y, int y_is_c128, int64_t
                          int neighbors, double eps, int round_begin, int round_end,
                          int finalize, double* saliency_state, double* out_posterior,
                          int32_t* out_peak, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* M  Oracle masks   extraction/mask_module.py:90-550                          */
+/* The images x are complex64 / complex128 and are read where they lie: the    */
+/* geometry names four collapsed axes (slowest first; unused ones have size 1)  */
+/* with the element strides of the input and of the output, besides the strides */
+/* of the source and of the sensor axis.  (..., K, D, F, T) and (..., K, F, T,  */
+/* D) are both expressed without a copy; the last collapsed axis runs along the */
+/* lanes.  All arithmetic is float64 on the widened input, rounded once.        */
+/* ------------------------------------------------------------------------- */
+typedef struct pbbss_mask_geom {
+  int64_t size[4];       /* pointwise: four independent axes; threshold masks: */
+                         /* [0], [1] index the row, [2], [3] the element of it */
+  int64_t x_stride[4];   /* element strides of the input along them            */
+  int64_t out_stride[4]; /* element strides of the output along them           */
+  int64_t x_source_stride;   /* pointwise: input stride of the source axis      */
+  int64_t x_sensor_stride;   /* input stride of the pooled sensor axis          */
+  int64_t out_source_stride; /* pointwise: output stride of the source axis     */
+  int64_t out_target_stride; /* quantile: output stride of the quantile axis    */
+  int32_t sources;           /* K, 1 <= K <= 9 (pointwise)                      */
+  int32_t sensors;           /* D, 1 <= D <= 34; 1 = no pooling                 */
+} pbbss_mask_geom;
+
+#define PBBSS_MASK_IBM 0    /* ideal_binary_mask    mask_module.py:90-136  */
+#define PBBSS_MASK_WIENER 1 /* wiener_like_mask     mask_module.py:139-179 */
+#define PBBSS_MASK_IRM 2    /* ideal_ratio_mask     mask_module.py:182-232 */
+#define PBBSS_MASK_IAM 3    /* ideal_amplitude_mask mask_module.py:235-287 */
+#define PBBSS_MASK_PSM 4    /* phase_sensitive_mask mask_module.py:290-322 */
+#define PBBSS_MASK_ICM 5    /* ideal_complex_mask   mask_module.py:325-347 */
+#define PBBSS_MASK_BIASED 6 /* biased_binary_mask   mask_module.py:496-550 */
+
+#define PBBSS_MASK_ST_NO_THRESHOLD 1 /* Lorenz: no element stays below the fraction
+                                        (all-zero row, or one element carries it all);
+                                        the reference raises ValueError there */
+
+/* M1  Pointwise masks, mask_module.py:90-347 and :496-550: one launch, one lane   */
+/* per point, the K sources (each pooled over the D sensors) in registers.  out:   */
+/* the real type of x (IBM, Wiener, IRM, IAM, PSM), the type of x (ICM; 0 / 0 is   */
+/* NaN as in the reference) or uint8 0 / 1 (biased binary).  IBM: arg-max over the */
+/* sources of the pooled power, first index among ties.  PSM is evaluated as       */
+/* Re(s conj(o)) / (|o| (|o| + eps)).  Biased binary: K = 2 (speech, noise), D = 1,*/
+/* table f64 (3, table_len) = 10^(speech threshold / 10), 10^(noise threshold /    */
+/* 10) and the cut flag (non-zero: speech 0, noise 1), indexed by the position on  */
+/* the last collapsed axis modulo table_len; table is NULL for the other modes.    */
+/* K > 9 or D > 34: PBBSS_ERR_UNSUPPORTED.                                         */
+int pbbss_mask_pointwise(pbbss_handle_t h, const void* x, int x_is_c128, int mode,
+                         const pbbss_mask_geom* geom, double eps, const double* table,
+                         int64_t table_len, void* out, void* stream);
+
+/* M2  lorenz_mask, mask_module.py:350-417.  Row value: |x|^2 summed over the D    */
+/* sensors.  Sorted descending with L_i = cumsum_i / sum, the threshold is the     */
+/* value at the last i with L_i < lorenz_fraction; out = value_high where the row  */
+/* value is > threshold (strict), value_low elsewhere, float32 or float64          */
+/* (out_is_f64).  out_status int32 (rows): PBBSS_MASK_ST_NO_THRESHOLD where no i   */
+/* qualifies (the row is then written as value_low).  Rows of at most 2048 values: */
+/* one launch, values in LDS.  Longer rows: values to a float64 workspace of the   */
+/* handle, an exact radix selection over their bit patterns (8 levels of a         */
+/* histogram and a pick launch; partial sums are added in a fixed order, no float  */
+/* atomics), and an apply pass on the same workspace values -- 20 launches.        */
+int pbbss_mask_lorenz(pbbss_handle_t h, const void* x, int x_is_c128,
+                      const pbbss_mask_geom* geom, double lorenz_fraction, double value_high,
+                      double value_low, void* out, int out_is_f64, int32_t* out_status,
+                      void* stream);
+
+/* M3  quantile_mask, mask_module.py:420-493.  Row value: |x| (D = 1).  For each   */
+/* of the num_quantiles <= 8 targets the threshold is a + (b - a) gamma (b - (b -  */
+/* a)(1 - gamma) for gamma >= 0.5, as NumPy's linear percentile) of the order      */
+/* statistics a = sorted[lower_rank], b = sorted[min(lower_rank + 1, N - 1)];      */
+/* gamma = 0 returns a exactly.  negative = 0: value > threshold, 1: value <       */
+/* threshold.  lower_rank, gamma and negative are HOST arrays, read during the     */
+/* call.  Target j is written at out + j * out_target_stride.  Paths as M2.        */
+int pbbss_mask_quantile(pbbss_handle_t h, const void* x, int x_is_c128,
+                        const pbbss_mask_geom* geom, int num_quantiles,
+                        const int64_t* lower_rank, const double* gamma, const int32_t* negative,
+                        double value_high, double value_low, void* out, int out_is_f64,
+                        int32_t* out_status, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* N2/N3  Real-embedding mixture components: von Mises-Fisher and spherical      */

@@ -116,6 +116,25 @@ class MixOpts(ctypes.Structure):
     ]
 
 
+MASK_IBM, MASK_WIENER, MASK_IRM, MASK_IAM, MASK_PSM, MASK_ICM, MASK_BIASED = range(7)
+MASK_ST_NO_THRESHOLD = 1
+
+
+class MaskGeom(ctypes.Structure):
+    """struct pbbss_mask_geom"""
+    _fields_ = [
+        ('size', ctypes.c_int64 * 4),
+        ('x_stride', ctypes.c_int64 * 4),
+        ('out_stride', ctypes.c_int64 * 4),
+        ('x_source_stride', ctypes.c_int64),
+        ('x_sensor_stride', ctypes.c_int64),
+        ('out_source_stride', ctypes.c_int64),
+        ('out_target_stride', ctypes.c_int64),
+        ('sources', ctypes.c_int32),
+        ('sensors', ctypes.c_int32),
+    ]
+
+
 # ---- the C ABI as data: argument types of every export of include/pbbss.h ---------------
 # (tests/test_capi_symbols.py compares the kind of every parameter with the header's prototypes)
 vp, i32, u32, i64, dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_int64, ctypes.c_double
@@ -206,6 +225,10 @@ SIGNATURES = {
         vp, vp, vp, vp, vp],
     'pbbss_deflation_seed': [vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, i32, dbl, i32, i32, i32,
         vp, vp, vp, vp],
+    'pbbss_mask_pointwise': [vp, vp, i32, i32, P(MaskGeom), dbl, vp, i64, vp, vp],
+    'pbbss_mask_lorenz': [vp, vp, i32, P(MaskGeom), dbl, dbl, dbl, vp, i32, vp, vp],
+    'pbbss_mask_quantile': [vp, vp, i32, P(MaskGeom), i32, i64p, P(dbl), i32p, dbl, dbl, vp, i32,
+        vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 
