@@ -238,7 +238,15 @@ int pbbss_cacg_m_step(pbbss_handle_t h, const void* y, int64_t B, int T, int D,
 /* ------------------------------------------------------------------------- */
 /* Batched Hermitian eigendecomposition (numpy.linalg.eigh as used at          */
 /* cacg.py:95 and extraction/beamformer.py:180).  a c128 (N,D,D) -> eigenvalues */
-/* ascending f64 (N,D), eigenvectors c128 (N,D,D) in columns.  D <= 32.        */
+/* ascending f64 (N,D), eigenvectors c128 (N,D,D) in columns.  D <= 34.        */
+/* Only the lower triangle is read.  status int32 (N) or NULL: 0, or            */
+/* PBBSS_ST_NONFINITE when that triangle holds a NaN or an Inf (the outputs of  */
+/* that matrix are then not to be used; NaN for D <= 8), or PBBSS_ST_EIG_NOCONV.*/
+/* Finite input of any magnitude is solved: a matrix whose largest entry lies   */
+/* outside [2^-400, 2^400] is solved as an exact power-of-two multiple.  (The   */
+/* alternative LDS Jacobi for D >= 9, chosen with PBBSS_GEN_HEEV=j, has no such */
+/* pre-scale: it reports PBBSS_ST_NONFINITE for a matrix whose squares overflow */
+/* or underflow, entries beyond about 1e+-136.)                                 */
 /* ------------------------------------------------------------------------- */
 int pbbss_heev_batched(pbbss_handle_t h, const void* a, int64_t N, int D,
                        double* out_eigval, void* out_eigvec,

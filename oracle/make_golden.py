@@ -8,6 +8,11 @@ Each fixture stores seeded inputs and the outputs of the unmodified reference
 functions (imported through oracle/refshim.py).  The committed fixtures pin
 both the NumPy oracle (tests/test_oracle_golden.py, CPU) and the HIP path
 (tests/test_gpu_golden.py) on boxes where the reference itself is absent.
+
+A second recipe needs no reference: `python -m oracle.make_solver_golden` rewrites
+tests/golden/solver_hard_cases.npz (ill-conditioned and badly scaled inputs of the
+small dense solvers with their 50-digit solutions; needs mpmath and scipy), and
+`--check` rebuilds it in memory and compares it with the committed file.
 """
 import os
 import warnings

@@ -14,6 +14,7 @@
 //   distribution/complex_angular_central_gaussian.py:34-55 normalize_observation
 #include "beamform.hpp"
 #include "cacgmm_em.hpp"
+#include "prescale.hpp"
 
 namespace pbbss {
 
@@ -79,16 +80,33 @@ __global__ void __launch_bounds__(kLaThreads) heev_kernel(const double* a, int64
     are = p[0];
     aim = (c.i == c.j) ? 0.0 : ((c.i > c.j) ? p[1] : -p[1]);
   }
+  // The Jacobi forms sum |a|^2 unscaled: entries beyond ~1e154 overflow it, entries below
+  // ~1e-162 underflow it, and either way it would hand back the diagonal as converged.  A matrix
+  // outside 2^+-400 is solved as its power-of-two multiple near one (exact both ways); a NaN or
+  // Inf anywhere in the triangle read is reported, with NaN results, instead of being rotated.
+  const bool bad = wave_or((isfinite(are) && isfinite(aim)) ? 0 : 1) != 0;
+  const int ex = pow2_prescale_exponent(wave_max(fmax(fabs(are), fabs(aim))));
+  if (ex != 0) {
+    are = ldexp(are, -ex);
+    aim = ldexp(aim, -ex);
+  }
   int sweeps = wave_jacobi_heev_tab<D>(are, aim, c, vre, vim, jtab, lane);
   double lam = lane_get(are, ij_lane(c.j, c.j));
   int rank = wave_sort_rank<D>(lam, c);
+  if (ex != 0) lam = ldexp(lam, ex);
+  if (bad) {
+    lam = __builtin_nan("");
+    vre = lam;
+    vim = lam;
+  }
   if (c.i < D && c.j < D) {
     double* ov = out_vec + ((n * D + c.i) * D + rank) * 2;
     ov[0] = vre;
     ov[1] = vim;
     if (c.i == 0) out_val[n * D + rank] = lam;
   }
-  if (status && lane == 0) status[n] = (sweeps < 0) ? PBBSS_ST_EIG_NOCONV : 0;
+  if (status && lane == 0)
+    status[n] = bad ? PBBSS_ST_NONFINITE : ((sweeps < 0) ? PBBSS_ST_EIG_NOCONV : 0);
 }
 
 // ------------------------------------------------------------------ GEV
@@ -134,6 +152,14 @@ __global__ void __launch_bounds__(kLaThreads) gev_kernel(const double* target,
   wave_adjoint(mre, mim, c, mtre, mtim);
   mre = 0.5 * (mre + mtre);
   mim = 0.5 * (mim + mtim);
+  // M = L^-1 Phi_xx L^-H is solved as 2^-e M (same eigenvectors): a pencil whose quotient leaves
+  // 2^+-400 would overflow or underflow the Jacobi's norm and come back as its diagonal
+  if (wave_or((isfinite(mre) && isfinite(mim)) ? 0 : 1)) st |= PBBSS_ST_NONFINITE;
+  const int ex = pow2_prescale_exponent(wave_max(fmax(fabs(mre), fabs(mim))));
+  if (ex != 0) {
+    mre = ldexp(mre, -ex);
+    mim = ldexp(mim, -ex);
+  }
   double vre, vim;
   int sweeps = wave_jacobi_heev_tab<D>(mre, mim, c, vre, vim, jtab, lane);
   if (sweeps < 0) st |= PBBSS_ST_EIG_NOCONV;
@@ -178,6 +204,16 @@ __global__ void __launch_bounds__(kLaThreads) solve_kernel(const double* A, cons
     const double* p = Bm + ((n * D + c.i) * M + c.j) * 2;
     bre = p[0];
     bim = p[1];
+  }
+  // |pivot|^2 overflows beyond ~1e154 and underflows below ~1e-162 (the quotient then comes out
+  // as 0 or Inf with no pivot exactly zero): such a system is solved as (2^-e A) X = 2^-e B.
+  // (Non-finite input propagates to X as it does through numpy.linalg.solve.)
+  const int ex = pow2_prescale_exponent(wave_max(fmax(fabs(are), fabs(aim))));
+  if (ex != 0) {
+    are = ldexp(are, -ex);
+    aim = ldexp(aim, -ex);
+    bre = ldexp(bre, -ex);
+    bim = ldexp(bim, -ex);
   }
   bool sing = wave_lu_solve<D>(are, aim, bre, bim, c, xre, xim);
   if (sing) wave_pinv_solve<D>(are, aim, bre, bim, c, xre, xim);  // math/solve.py:111-113

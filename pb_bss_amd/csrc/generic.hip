@@ -22,6 +22,7 @@
 #include "generic.hpp"
 #include <cmath>
 #include "generic_dev.hpp"
+#include "prescale.hpp"
 #include <cstdlib>
 #include <type_traits>
 
@@ -770,10 +771,17 @@ __global__ void __launch_bounds__(NT) gen_heev_kernel(GenHeev g) {
     for (int e = tid; e < DP * DP * 2; e += NT) A[e] *= it;
   }
   __syncthreads();
-  double fro2 = 0.0;
-  for (int e = tid; e < DP * DP; e += NT) fro2 += A[e * 2] * A[e * 2] + A[e * 2 + 1] * A[e * 2 + 1];
+  double fro2 = 0.0, nz = 0.0;
+  for (int e = tid; e < DP * DP; e += NT) {
+    fro2 += A[e * 2] * A[e * 2] + A[e * 2 + 1] * A[e * 2 + 1];
+    nz += (A[e * 2] != 0.0 || A[e * 2 + 1] != 0.0) ? 1.0 : 0.0;
+  }
   fro2 = gen_block_sum<NT>(fro2, red, tid);
+  nz = gen_block_sum<NT>(nz, red, tid);
   if (!isfinite(fro2)) st |= PBBSS_ST_NONFINITE;
+  // a non-zero matrix whose squares underflow would come back as its diagonal: say so (this
+  // solver has no pre-scaling; the QL kernel, which serves every call by default, has)
+  if (nz > 0.0 && !(fro2 >= 0x1p-900)) st |= PBBSS_ST_NONFINITE;
   const GenJacobiScratch scratch{A2, V2, rot, red, part};
   if (lds_jacobi_heev<NT>(A, V, scratch, D, DP, tid) < 0) st |= PBBSS_ST_EIG_NOCONV;
   __syncthreads();
@@ -855,7 +863,7 @@ __global__ void __launch_bounds__(kWave) gen_heev_ql_kernel(GenHeev g) {
   double* wbuf = vbuf + 2 * DP;                 // [DP][2]
   int st = 0;
   // ---- load (lower triangle, like gen_heev_kernel), optional trace normalisation
-  double tr = 0.0;
+  double tr = 0.0, amax = 0.0;
   for (int e = lane; e < n * n; e += kWave) {
     const int i = e / n, j = e - i * n;
     const int lo = i < j ? j : i, hi = i < j ? i : j;
@@ -863,18 +871,28 @@ __global__ void __launch_bounds__(kWave) gen_heev_ql_kernel(GenHeev g) {
     const double re = p[0];
     const double im = (i == j) ? 0.0 : ((i > j) ? p[1] : -p[1]);
     if (i == j) tr += re;
+    amax = fmax(amax, fmax(fabs(re), fabs(im)));
     A[(i * LD + j) * 2] = re;
     A[(i * LD + j) * 2 + 1] = im;
     Zt[i * LD + j] = (i == j) ? 1.0 : 0.0;
   }
   tr = wave_sum(tr);
+  // plain eigh (the stand-alone call): a matrix outside 2^+-400 is solved as its power-of-two
+  // multiple near one -- the squares of the norm, the reflectors and the QL rotations (and the
+  // absolute floor under them) would otherwise leave the float64 range and the solver return
+  // the diagonal, or garbage, as converged.  Exact both ways; 0 for every covariance of the EM.
+  const int ex = (g.covariance_norm < 0) ? pow2_prescale_exponent(wave_max(amax)) : 0;
   __syncthreads();
   double fro2 = 0.0;
   {
     const double it = (g.covariance_norm == PBBSS_COVNORM_TRACE) ? 1.0 / fmax(tr, kTiny) : 1.0;  // cacg.py:88-90
     for (int e = lane; e < n * n; e += kWave) {
       const int i = e / n, j = e - i * n;
-      const double re = A[(i * LD + j) * 2] * it, im = A[(i * LD + j) * 2 + 1] * it;
+      double re = A[(i * LD + j) * 2] * it, im = A[(i * LD + j) * 2 + 1] * it;
+      if (ex != 0) {
+        re = ldexp(re, -ex);
+        im = ldexp(im, -ex);
+      }
       A[(i * LD + j) * 2] = re;
       A[(i * LD + j) * 2 + 1] = im;
       fro2 += re * re + im * im;
@@ -896,7 +914,7 @@ __global__ void __launch_bounds__(kWave) gen_heev_ql_kernel(GenHeev g) {
     lmax = fmax(lmax, lm);
   }
   if (lane < n) {
-    const double l = dreg;
+    const double l = (ex != 0) ? ldexp(dreg, ex) : dreg;
     double lout = l;
     if (g.covariance_norm == PBBSS_COVNORM_EIGENVALUE) {  // cacg.py:112-121
       lout = l / fmax(lmax, kTiny);

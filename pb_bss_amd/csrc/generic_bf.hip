@@ -7,6 +7,7 @@
 #include "generic_bf.hpp"
 #include <cmath>
 #include "generic_dev.hpp"
+#include "prescale.hpp"
 
 namespace pbbss {
 namespace {
@@ -82,6 +83,24 @@ __global__ void __launch_bounds__(kGenThreads)
   load_mat(A, n, D, D, w.A, tid);
   load_mat(Bm, n, D, M, w.B, tid);
   __syncthreads();
+  {
+    // |pivot|^2 leaves the float64 range for entries beyond ~1e+-154 and the quotients come out
+    // as 0 or Inf with no pivot exactly zero: such a system is solved as (2^-e A) X = 2^-e B
+    double amax = 0.0;
+    for (int e = tid; e < kMat; e += kGenThreads) amax = fmax(amax, fabs(w.A[e]));
+    amax = wave_max(amax);
+    if ((tid & 63) == 0) w.S.red[tid >> 6] = amax;
+    __syncthreads();
+    for (int v = 0; v < kGenWaves; ++v) amax = fmax(amax, w.S.red[v]);
+    const int ex = pow2_prescale_exponent(amax);
+    if (ex != 0) {
+      for (int e = tid; e < kMat; e += kGenThreads) {
+        w.A[e] = ldexp(w.A[e], -ex);
+        w.B[e] = ldexp(w.B[e], -ex);
+      }
+    }
+    __syncthreads();
+  }
   const bool sing = stable_solve(w, D, M, tid);
   for (int e = tid; e < D * M; e += kGenThreads) {
     const int i = e / M, j = e - i * M;
@@ -340,6 +359,8 @@ __global__ void __launch_bounds__(kGenThreads)
       fro2 += G[(i * LD + j) * 2] * G[(i * LD + j) * 2] + G[(i * LD + j) * 2 + 1] * G[(i * LD + j) * 2 + 1];
     }
     fro2 = wave_sum(fro2);
+    // a quotient M = L^-1 T L^-H that overflows (or a NaN) is reported, not returned as e_top
+    if (!isfinite(fro2)) st |= PBBSS_ST_NONFINITE;
     double lam, xre[LD], xim[LD];
     if (wave_heev_ql<LD>(G, LD, Zt, LD, dv, ev, tauv, vbuf, wbuf, D, lane,
                          (fro2 > 0.0) && isfinite(fro2), lam, xre, xim))

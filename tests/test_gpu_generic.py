@@ -13,6 +13,7 @@ def _cov(vec, val):
 
 @pytest.mark.parametrize('D', [9, 12, 16, 17, 24, 32, 33, 34])
 def test_heev_matches_eigh(D):
+    # well-conditioned input only; ill-conditioned / badly scaled cases: test_gpu_solvers_hard.py
     from pb_bss_amd import _lib, engine
     rng = np.random.default_rng(D)
     a = rng.standard_normal((7, D, D)) + 1j * rng.standard_normal((7, D, D))

@@ -29,6 +29,7 @@ def _posdef(rng, N, D):
 
 @pytest.mark.parametrize('D', [2, 3, 4, 5, 6, 7, 8])
 def test_heev_matches_eigh(D):
+    # well-conditioned input only; ill-conditioned / badly scaled cases: test_gpu_solvers_hard.py
     from pb_bss_amd import engine
     rng = np.random.default_rng(D)
     N = 257
