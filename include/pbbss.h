@@ -644,6 +644,64 @@ int pbbss_mask_quantile(pbbss_handle_t h, const void* x, int x_is_c128,
                         int32_t* out_status, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* V  Evaluation metrics   evaluation/module_si_sdr.py, evaluation/sxr_module.py */
+/* Streaming reductions over the N samples of time signals (csrc/eval.hip).     */
+/* Every workgroup owns a fixed span of 4096 samples, writes its float64        */
+/* partial sums to the handle's workspace and a finishing kernel adds them in   */
+/* span order: no float atomics, results are bit-identical from call to call.   */
+/* float32 input is widened in registers; arithmetic and results are float64.   */
+/* Divisions by zero give inf / nan as in NumPy.  A sample count N < 1, a batch  */
+/* < 1 or a signal pointer that is no multiple of the size of one real (4 or 8   */
+/* bytes) is PBBSS_ERR_INVALID_ARG.  One launch covers all items: more than      */
+/* 2^24 - 1 workgroups (items x ceil(reals per row / 4096)) is                   */
+/* PBBSS_ERR_UNSUPPORTED.                                                        */
+/* ------------------------------------------------------------------------- */
+#define PBBSS_EVAL_F32 0  /* float32                                   */
+#define PBBSS_EVAL_F64 1  /* float64                                   */
+#define PBBSS_EVAL_C64 2  /* complex64  (interleaved re, im float32)   */
+#define PBBSS_EVAL_C128 3 /* complex128 (interleaved re, im float64)   */
+
+/* V1  get_variance_for_zero_mean_signal / get_snr, sxr_module.py:17-48: the    */
+/* mean of re^2 + im^2 of each of `rows` rows of `length` consecutive elements, */
+/* row r starting at x + r * row_stride elements.  out float64 (rows).          */
+int pbbss_signal_power(pbbss_handle_t h, const void* x, int dtype, int64_t rows, int64_t length,
+                       int64_t row_stride, double* out, void* stream);
+
+/* V2  si_sdr, module_si_sdr.py:4-56, for all Kr x Ke pairs of B batch items in  */
+/* two reads of the rows: sum r_i^2 and sum r_i e_j first, then the residual     */
+/* energy sum (e_j - alpha_ij r_i)^2 with alpha_ij = sum r_i e_j / sum r_i^2,    */
+/* and out[b, i, j] = 10 log10(alpha_ij^2 sum r_i^2 / residual), float64         */
+/* (B, Kr, Ke).  Row i of item b of the reference starts at reference + b *      */
+/* ref_batch_stride + i * ref_row_stride elements (estimation alike); a stride   */
+/* may be 0 (broadcast); samples are consecutive.  Row-wise pairs: Kr = Ke = 1.  */
+/* 1 <= Kr, Ke <= 8, else PBBSS_ERR_UNSUPPORTED.                                 */
+int pbbss_si_sdr(pbbss_handle_t h, const void* reference, const void* estimation, int is_f64,
+                 int64_t B, int Kr, int Ke, int64_t N, int64_t ref_batch_stride,
+                 int64_t ref_row_stride, int64_t est_batch_stride, int64_t est_row_stride,
+                 double* out, void* stream);
+
+/* V3  output_sxr, sxr_module.py:168-274.  contributions (B, Ks, Kt, N) and      */
+/* noise (B, Kt, N), contiguous, of type `dtype`.  Per batch item the selection  */
+/* of Ks of the Kt outputs with the largest sum of S[k, sel[k]] -- enumerated in */
+/* itertools.permutations order, first maximum -- goes to out_selection int64    */
+/* (B, Ks); out_sxr float64 (B, 3, Ks) holds SDR, SIR, SNR per source;           */
+/* out_mean float64 (B, 3) their means over the sources, written when            */
+/* average_sources is non-zero (may be NULL otherwise).                          */
+/* 1 <= Ks <= Kt <= 8, else PBBSS_ERR_UNSUPPORTED (Ks > Kt: INVALID_ARG).        */
+int pbbss_output_sxr(pbbss_handle_t h, const void* contributions, const void* noise, int dtype,
+                     int64_t B, int Ks, int Kt, int64_t N, int average_sources, double* out_sxr,
+                     int64_t* out_selection, double* out_mean, void* stream);
+
+/* V4  input_sxr, sxr_module.py:94-165.  images (B, K, D, N) and noise (B, D, N), */
+/* contiguous, of type `dtype`.  out float64 (B, 3, Ko, Do): SDR, SIR, SNR with   */
+/* Ko = 1 if average_sources else K and Do = 1 if average_channels else D.        */
+/* 1 <= K <= 9, 1 <= D <= 29 (the reference's asserts), else                      */
+/* PBBSS_ERR_UNSUPPORTED.                                                         */
+int pbbss_input_sxr(pbbss_handle_t h, const void* images, const void* noise, int dtype, int64_t B,
+                    int K, int D, int64_t N, int average_sources, int average_channels,
+                    double* out, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* N2/N3  Real-embedding mixture components: von Mises-Fisher and spherical      */
 /* Gaussian (distribution/von_mises_fisher.py:33-144, gaussian.py:100-193).      */
 /* y (B,N,E) real, row-major, float32 or float64 (y_is_f64); 1 <= E <= 256,      */

@@ -118,6 +118,7 @@ class MixOpts(ctypes.Structure):
 
 MASK_IBM, MASK_WIENER, MASK_IRM, MASK_IAM, MASK_PSM, MASK_ICM, MASK_BIASED = range(7)
 MASK_ST_NO_THRESHOLD = 1
+EVAL_F32, EVAL_F64, EVAL_C64, EVAL_C128 = range(4)
 
 
 class MaskGeom(ctypes.Structure):
@@ -229,6 +230,10 @@ SIGNATURES = {
     'pbbss_mask_lorenz': [vp, vp, i32, P(MaskGeom), dbl, dbl, dbl, vp, i32, vp, vp],
     'pbbss_mask_quantile': [vp, vp, i32, P(MaskGeom), i32, i64p, P(dbl), i32p, dbl, dbl, vp, i32,
         vp, vp],
+    'pbbss_signal_power': [vp, vp, i32, i64, i64, i64, vp, vp],
+    'pbbss_si_sdr': [vp, vp, vp, i32, i64, i32, i32, i64, i64, i64, i64, i64, vp, vp],
+    'pbbss_output_sxr': [vp, vp, vp, i32, i64, i32, i32, i64, i32, vp, vp, vp, vp],
+    'pbbss_input_sxr': [vp, vp, vp, i32, i64, i32, i32, i64, i32, i32, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 
