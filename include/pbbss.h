@@ -967,6 +967,55 @@ int pbbss_istft(pbbss_handle_t h, const void* X, int x_is_c128, int64_t C, int T
                 double* out, int64_t n_out, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* (W)  k-means on real embeddings: what BinaryGMM / BinaryGMMTrainer           */
+/* (pb_bss/distribution/gmm.py:176-230) hand to sklearn's KMeans, on the device. */
+/* y (B, N, E) float32 / float64 row-major; all arithmetic float64 on the        */
+/* exactly widened values; the squared distance is the direct sum of             */
+/* (y_e - c_e)^2.  1 <= K <= 64, 1 <= E <= 256, N < 2^31, any B that fits one    */
+/* grid (PBBSS_ERR_UNSUPPORTED beyond).  saliency (B, N) uint8 or NULL: rows     */
+/* with 0 take part in no statistic.  Every floating-point sum has a fixed       */
+/* order: two calls on the same input give the same bits.                        */
+/*                                                                               */
+/* pbbss_kmeans_fit replaces sklearn's Lloyd loop (_kmeans_single_lloyd): one    */
+/* sweep over the rows per iteration (labels = argmin, lowest index wins a tie;  */
+/* class sums, counts, inertia and the number of moved labels as ordered         */
+/* partials), then per problem the new centres with sklearn's empty-cluster      */
+/* relocation (the n_empty selected rows farthest from their centres, farthest   */
+/* first, become the empty classes in ascending order), the total squared shift  */
+/* and the stop: no label moved (strict), else shift <= tol * mean_e var_n y,    */
+/* else max_iter.  After a non-strict stop one more sweep assigns the labels to  */
+/* the final centres; out_inertia belongs to the final centres and labels;       */
+/* out_n_iter counts as sklearn's n_iter_.  The stop is taken on the device:     */
+/* iterations are enqueued `block` at a time, those behind the stop return at    */
+/* once, and the host waits for the stream once per block (the only host         */
+/* synchronisation).  The results do not depend on `block`.  A problem that      */
+/* selects fewer than K rows: PBBSS_ERR_INVALID_ARG.                             */
+/*                                                                               */
+/* pbbss_kmeans_predict: labels, optionally the one-hot affiliation (B, K, N) in */
+/* the dtype of y and the inertia, one launch.                                   */
+/*                                                                               */
+/* pbbss_kmeans_plusplus replaces sklearn's greedy kmeans_plusplus.  The host    */
+/* draws randoms (B, 1 + (K - 1) trials) in sklearn's order (the uniform behind  */
+/* choice(n, p=uniform), then uniform(size=trials) per step; trials = 2 +        */
+/* int(log K), at most 8); the device does the ordered float64 prefix sum of     */
+/* closest_dist_sq over the selected rows (chunk sums, a scan of the chunk sums, */
+/* a scan within a chunk), the searchsorted of the scaled draws, the potentials  */
+/* of all candidates in one pass (first minimum wins) and the update.  The first */
+/* index goes through the same search on the 0/1 mask.                           */
+/* ------------------------------------------------------------------------- */
+int pbbss_kmeans_fit(pbbss_handle_t h, const void* y, int y_is_f64, int64_t B, int64_t N, int E,
+                     int K, const uint8_t* saliency, const double* in_centers, int max_iter,
+                     double tol, int block, double* out_centers, int32_t* out_labels,
+                     double* out_inertia, int32_t* out_n_iter, void* stream);
+int pbbss_kmeans_predict(pbbss_handle_t h, const void* y, int y_is_f64, int64_t B, int64_t N,
+                         int E, int K, const double* centers, int32_t* out_labels,
+                         void* out_one_hot, double* out_inertia, void* stream);
+int pbbss_kmeans_plusplus(pbbss_handle_t h, const void* y, int y_is_f64, int64_t B, int64_t N,
+                          int E, int K, const uint8_t* saliency, int trials,
+                          const double* randoms, int32_t* out_indices, double* out_centers,
+                          void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Timing hook for bench.py: runs `fit` with HIP events recorded on `stream`   */
 /* around the EM kernel launch(es) only and returns the elapsed milliseconds   */
 /* of the most recent call (the roofline figure needs the kernel duration on   */

@@ -234,6 +234,10 @@ SIGNATURES = {
     'pbbss_si_sdr': [vp, vp, vp, i32, i64, i32, i32, i64, i64, i64, i64, i64, vp, vp],
     'pbbss_output_sxr': [vp, vp, vp, i32, i64, i32, i32, i64, i32, vp, vp, vp, vp],
     'pbbss_input_sxr': [vp, vp, vp, i32, i64, i32, i32, i64, i32, i32, vp, vp],
+    'pbbss_kmeans_fit': [vp, vp, i32, i64, i64, i32, i32, vp, vp, i32, dbl, i32, vp, vp, vp, vp,
+        vp],
+    'pbbss_kmeans_predict': [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp],
+    'pbbss_kmeans_plusplus': [vp, vp, i32, i64, i64, i32, i32, vp, i32, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -14,7 +14,7 @@ from .cbmm import CBMM, CBMMTrainer
 from .von_mises_fisher import VonMisesFisher, VonMisesFisherTrainer
 from .vmfmm import VMFMM, VMFMMTrainer
 from .gaussian import DiagonalGaussian, Gaussian, SphericalGaussian, GaussianTrainer
-from .gmm import GMM, GMMTrainer
+from .gmm import GMM, GMMTrainer, BinaryGMM, BinaryGMMTrainer
 from .gcacgmm import GCACGMM, GCACGMMTrainer
 from .vmfcacgmm import VMFCACGMM, VMFCACGMMTrainer
 
@@ -22,7 +22,8 @@ __all__ = [
     'CACGMM', 'CACGMMTrainer', 'CWMM', 'CWMMTrainer', 'CBMM', 'CBMMTrainer',
     'ComplexBingham', 'ComplexBinghamTrainer',
     'VonMisesFisher', 'VonMisesFisherTrainer', 'VMFMM', 'VMFMMTrainer',
-    'Gaussian', 'DiagonalGaussian', 'SphericalGaussian', 'GaussianTrainer', 'GMM', 'GMMTrainer', 'GCACGMM', 'GCACGMMTrainer',
+    'Gaussian', 'DiagonalGaussian', 'SphericalGaussian', 'GaussianTrainer', 'GMM', 'GMMTrainer',
+    'BinaryGMM', 'BinaryGMMTrainer', 'GCACGMM', 'GCACGMMTrainer',
     'VMFCACGMM', 'VMFCACGMMTrainer',
     'ComplexWatson', 'ComplexWatsonTrainer',
     'ComplexAngularCentralGaussian', 'ComplexAngularCentralGaussianTrainer',

@@ -6,8 +6,9 @@ model the joint GCACGMM uses, gcacgmm.py:141; the vMF mixture's E-step / M-step 
 raw embedding): the whole EM loop is one C-ABI call (`pbbss_gmm_full_fit` / `pbbss_gmm_fit`).
 covariance_type 'diagonal' and the `weight_constant_axis` sets beyond (-1,), (-2,), -2 run the
 reference's loop step by step on the device (`_embed_stepwise.py`: log-pdf, softmax, weight and
-single-Gaussian fit kernels, no host round trip inside the loop).  BinaryGMM wraps sklearn's
-KMeans and is out of scope.
+single-Gaussian fit kernels, no host round trip inside the loop).  `BinaryGMM` and
+`BinaryGMMTrainer` (:176-230, k-means through sklearn in the reference) live in kmeans.py on the
+kernels of csrc/kmeans.hip and are exported from here as in the reference module.
 """
 from dataclasses import dataclass
 
@@ -17,12 +18,13 @@ from .. import _lib, engine
 from . import _embed_stepwise as sw
 from . import _mixture as mix
 from .gaussian import DiagonalGaussian, Gaussian, SphericalGaussian
+from .kmeans import BinaryGMM, BinaryGMMTrainer, KMeans  # noqa: F401  (KMeans: the name gmm.py imports)
 from .utils import _ProbabilisticModel, as_result
 from ..utils import labels_to_one_hot  # noqa: F401  (names the reference module exposes)
 from .gaussian import GaussianTrainer  # noqa: F401  (names the reference module exposes)
 from .mixture_model_utils import estimate_mixture_weight, log_pdf_to_affiliation  # noqa: F401  (names the reference module exposes)
 
-__all__ = ['GMM', 'GMMTrainer']
+__all__ = ['GMM', 'GMMTrainer', 'BinaryGMM', 'BinaryGMMTrainer']
 
 
 _CLASS, _UNIFORM, _ONES = _lib.WEIGHT_PER_CLASS_MEAN, _lib.WEIGHT_UNIFORM, mix.WEIGHT_ONES
