@@ -58,6 +58,7 @@ extern "C" {
 #define PBBSS_ST_NOT_POSDEF 16u    /* Cholesky of B failed (GEV: LAPACK INFO > N)  */
 #define PBBSS_ST_SINGULAR 32u      /* LU met a zero pivot (np.linalg.LinAlgError)  */
 #define PBBSS_ST_SOLVE_NOCONV 64u  /* complex Bingham parameter solve did not converge */
+#define PBBSS_ST_ZERO_SIGNAL 128u  /* BSS-Eval: an all-zero reference or estimate (mir_eval: ValueError) */
 
 typedef struct pbbss_handle_s* pbbss_handle_t;
 
@@ -644,7 +645,7 @@ int pbbss_mask_quantile(pbbss_handle_t h, const void* x, int x_is_c128,
                         int32_t* out_status, void* stream);
 
 /* ------------------------------------------------------------------------- */
-/* V  Evaluation metrics   evaluation/module_si_sdr.py, evaluation/sxr_module.py */
+/* V  Evaluation metrics   evaluation/module_si_sdr.py, sxr_module.py, module_mir_eval.py */
 /* Streaming reductions over the N samples of time signals (csrc/eval.hip).     */
 /* Every workgroup owns a fixed span of 4096 samples, writes its float64        */
 /* partial sums to the handle's workspace and a finishing kernel adds them in   */
@@ -700,6 +701,74 @@ int pbbss_output_sxr(pbbss_handle_t h, const void* contributions, const void* no
 int pbbss_input_sxr(pbbss_handle_t h, const void* images, const void* noise, int dtype, int64_t B,
                     int K, int D, int64_t N, int average_sources, int average_channels,
                     double* out, void* stream);
+
+/* V5-V9  BSS-Eval SDR / SIR / SAR (Vincent et al. 2006, BSS Eval 3.0): replaces  */
+/* mir_eval.separation.bss_eval_sources as evaluation/module_mir_eval.py:5-91     */
+/* calls it, and _bss_eval_sources_and_noise, module_mir_eval.py:94-141, for      */
+/* K + 1 estimates (csrc/bss_eval.hip).  reference (B, K, N) and estimation       */
+/* (B, Ke, N) of type `dtype` (PBBSS_EVAL_F32 or PBBSS_EVAL_F64), element strides  */
+/* as in pbbss_si_sdr, samples consecutive.  ref_batch_stride == 0: the same       */
+/* references for every item, correlated and factorised once.  Each estimate,      */
+/* zero-padded to N + filter_length - 1 samples, is projected by least squares     */
+/* onto the filter_length delays of reference j and onto those of all references;  */
+/* float64 arithmetic, ordered sums, bit-identical from call to call.  Limits:     */
+/* 1 <= K <= 8, Ke in {K, K + 1}, Ke <= 8 (OutputMetrics.check_inputs),            */
+/* 1 <= filter_length <= 512, compute_permutation == 0 only with Ke == K (the      */
+/* reference's NotImplementedError), else PBBSS_ERR_UNSUPPORTED.                   */
+
+/* V5  bytes of the handle's workspace one call takes (items are processed in      */
+/* groups that fit 1 GiB; one item always runs).                                   */
+int pbbss_bss_eval_workspace(int64_t B, int K, int Ke, int64_t N, int64_t ref_batch_stride,
+                             int filter_length, int64_t* out_bytes);
+
+/* V6  bss_eval_sources / _bss_eval_sources_and_noise.  out_sdr, out_sir, out_sar  */
+/* float64 (B, K) and out_selection int64 (B, K): with compute_permutation the     */
+/* ordered pick of K estimates with the largest mean SIR, enumerated in            */
+/* itertools.permutations order, first maximum; without it estimate j against      */
+/* reference j and selection = 0 .. K - 1.  out_tables float64 (B, 3, Ke, K) or    */
+/* NULL: SDR, SIR, SAR of every estimate against every reference (NaN for the      */
+/* pairs a call without the search skips).  out_status int32 (B):                  */
+/* PBBSS_ST_NOT_POSDEF where the Cholesky factorisation met a pivot not larger     */
+/* than n 2^-52 times its original diagonal entry (the values of that item are not */
+/* to be used: solve pbbss_bss_eval_system on the host and call                    */
+/* pbbss_bss_eval_filters), PBBSS_ST_ZERO_SIGNAL for an all-zero row.              */
+int pbbss_bss_eval(pbbss_handle_t h, const void* reference, const void* estimation, int dtype,
+                   int64_t B, int K, int Ke, int64_t N, int64_t ref_batch_stride,
+                   int64_t ref_row_stride, int64_t est_batch_stride, int64_t est_row_stride,
+                   int filter_length, int compute_permutation, double* out_sdr, double* out_sir,
+                   double* out_sar, int64_t* out_selection, double* out_tables,
+                   int32_t* out_status, void* stream);
+
+/* V7  the normal equations mir_eval.separation._project builds: out_gram float64  */
+/* (Bref, K L, K L), Bref = 1 if ref_batch_stride == 0 else B, entry               */
+/* (i L + l, j L + m) = sum_n s_i[n - l] s_j[n - m]; out_rhs float64 (B, Ke, K L), */
+/* entry i L + l = sum_n s_i[n - l] e[n].                                          */
+int pbbss_bss_eval_system(pbbss_handle_t h, const void* reference, const void* estimation,
+                          int dtype, int64_t B, int K, int Ke, int64_t N,
+                          int64_t ref_batch_stride, int64_t ref_row_stride,
+                          int64_t est_batch_stride, int64_t est_row_stride, int filter_length,
+                          double* out_gram, double* out_rhs, void* stream);
+
+/* V8  pbbss_bss_eval with the filters supplied (the lstsq branch of _project):    */
+/* filters_all float64 (B, Ke, K L) projects estimate e onto all references,       */
+/* filters_single (B, Ke, K, L) onto reference j alone.  out_status is 0.          */
+int pbbss_bss_eval_filters(pbbss_handle_t h, const void* reference, const void* estimation,
+                           int dtype, int64_t B, int K, int Ke, int64_t N,
+                           int64_t ref_batch_stride, int64_t ref_row_stride,
+                           int64_t est_batch_stride, int64_t est_row_stride, int filter_length,
+                           int compute_permutation, const double* filters_all,
+                           const double* filters_single, double* out_sdr, double* out_sir,
+                           double* out_sar, int64_t* out_selection, double* out_tables,
+                           int32_t* out_status, void* stream);
+
+/* V9  Device time in ms of the four phases of the handle's last pbbss_bss_eval    */
+/* made with pbbss_set_timing on: correlations and assembly, factorisation,        */
+/* triangular solves, synthesis and epilogue.  Such a call brackets its phases     */
+/* with events and WAITS for the device before it returns; with timing off (the    */
+/* default) pbbss_bss_eval stays asynchronous and these values are not touched.    */
+/* Measurement aid of tools/bench_bss_eval.py; no reference counterpart.           */
+/* out_ms float32 (4).                                                             */
+int pbbss_bss_eval_phase_ms(pbbss_handle_t h, float* out_ms);
 
 /* ------------------------------------------------------------------------- */
 /* N2/N3  Real-embedding mixture components: von Mises-Fisher and spherical      */

@@ -28,6 +28,7 @@ ST_SLOWPATH = 8
 ST_NOT_POSDEF = 16
 ST_SINGULAR = 32
 ST_SOLVE_NOCONV = 64  # complex Bingham parameter solve did not converge
+ST_ZERO_SIGNAL = 128  # BSS-Eval: an all-zero reference or estimate
 
 COVNORM = {False: 0, None: 0, 'eigenvalue': 1, 'trace': 2}
 WEIGHT_PER_CLASS_MEAN = 0
@@ -234,6 +235,14 @@ SIGNATURES = {
     'pbbss_si_sdr': [vp, vp, vp, i32, i64, i32, i32, i64, i64, i64, i64, i64, vp, vp],
     'pbbss_output_sxr': [vp, vp, vp, i32, i64, i32, i32, i64, i32, vp, vp, vp, vp],
     'pbbss_input_sxr': [vp, vp, vp, i32, i64, i32, i32, i64, i32, i32, vp, vp],
+    'pbbss_bss_eval_workspace': [i64, i32, i32, i64, i64, i32, i64p],
+    'pbbss_bss_eval': [vp, vp, vp, i32, i64, i32, i32, i64, i64, i64, i64, i64, i32, i32, vp, vp,
+        vp, vp, vp, vp, vp],
+    'pbbss_bss_eval_system': [vp, vp, vp, i32, i64, i32, i32, i64, i64, i64, i64, i64, i32, vp, vp,
+        vp],
+    'pbbss_bss_eval_filters': [vp, vp, vp, i32, i64, i32, i32, i64, i64, i64, i64, i64, i32, i32,
+        vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    'pbbss_bss_eval_phase_ms': [vp, f32p],
     'pbbss_kmeans_fit': [vp, vp, i32, i64, i64, i32, i32, vp, vp, i32, dbl, i32, vp, vp, vp, vp,
         vp],
     'pbbss_kmeans_predict': [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp],

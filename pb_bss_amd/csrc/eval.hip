@@ -15,6 +15,7 @@
 // estimate that is c * reference with c a power of two has alpha == c exactly and a residual of
 // exactly zero (the reference's doctests return inf there).
 #include "eval.hpp"
+#include "eval_dev.hpp"
 
 #include <math.h>
 
@@ -41,12 +42,6 @@ struct Wide<double> {
     d[0] = v.x, d[1] = v.y;
   }
 };
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 __device__ inline unsigned low4(const void* p) {
   return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u);
@@ -195,13 +190,6 @@ __global__ __launch_bounds__(kEvalThreads) void rows_kernel(EvalRows g, int64_t 
   }
 }
 
-// sum of the `chunks` partials of one accumulator, in span order
-__device__ inline double span_sum(const double* p, int64_t chunks, int64_t stride) {
-  double s = p[0];
-  for (int64_t w = 1; w < chunks; ++w) s += p[w * stride];
-  return s;
-}
-
 // out[b, a] = sum over the spans (/ divisor when it is not zero)
 __global__ __launch_bounds__(256) void finish_sum_kernel(const double* __restrict__ partials,
                                                          int64_t total, int64_t chunks, int A,
@@ -232,69 +220,9 @@ __global__ __launch_bounds__(256) void si_sdr_finish_kernel(const double* __rest
   out[idx] = 10.0 * log10(al * al * rr / res);
 }
 
-// ---- NumPy's summation order for a short run of float64 (add.reduce along a contiguous axis):
-// fewer than 8 addends one after the other from zero, otherwise eight running sums over the
-// blocks of eight, combined as a tree, and the remainder one after the other.
-__device__ inline double np_sum(const double* a, int n, int stride) {
-  if (n < 8) {
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s += a[i * stride];
-    return s;
-  }
-  double r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = a[j * stride];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] += a[(i + j) * stride];
-  }
-  double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) s += a[i * stride];
-  return s;
-}
-
 __device__ inline double sxr_db(double s, double x) { return 10.0 * log10(s / x); }
 
 // ---- output_sxr ---------------------------------------------------------------------------
-// selection number p (itertools.permutations(range(Kt), Ks) order) -> sel[0..Ks)
-__device__ inline void unrank_selection(int p, int Ks, int Kt, const int (&radix)[kSxrMaxTargets],
-                                        int (&sel)[kSxrMaxTargets]) {
-  unsigned used = 0;
-#pragma unroll
-  for (int k = 0; k < kSxrMaxTargets; ++k) {
-    sel[k] = 0;
-    if (k < Ks) {
-      int d = p / radix[k];
-      p -= d * radix[k];
-      int pick = 0;
-      bool found = false;
-#pragma unroll
-      for (int t = 0; t < kSxrMaxTargets; ++t) {
-        const bool is_free = t < Kt && !((used >> t) & 1u);
-        if (is_free && !found) {
-          if (d == 0) {
-            pick = t;
-            found = true;
-          }
-          --d;
-        }
-      }
-      sel[k] = pick;
-      used |= 1u << pick;
-    }
-  }
-}
-
-// is candidate (va, pa) ahead of (vb, pb) for np.argmax: larger value, NaN ahead of everything,
-// lower index among equals
-__device__ inline bool ahead(double va, int pa, double vb, int pb) {
-  const bool na = va != va, nb = vb != vb;
-  if (na != nb) return na;
-  if (!na && va != vb) return va > vb;
-  return pa < pb;
-}
-
 // one wave per batch item.  pS (B Ks Kt, chunks), pN (B Kt, chunks): span partials of sum |x|^2.
 __global__ __launch_bounds__(64) void output_sxr_kernel(const double* __restrict__ pS,
                                                         const double* __restrict__ pN,

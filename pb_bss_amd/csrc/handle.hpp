@@ -3,6 +3,7 @@
 #pragma once
 #include "pbbss.h"
 #include <mutex>
+#include "carver.hpp"
 #include "embed.hpp"
 #include "embed_wide.hpp"
 #include "em_launch.hpp"
@@ -46,6 +47,7 @@ struct pbbss_handle_s {
   unsigned ring_seq = 0;         // timed regions started so far
   hipEvent_t gate_ev = nullptr;  // completion of this handle's last launch with inter-workgroup waits
   int gate_dev = -1;  // device index of the residency gate this handle takes part in (-1: none)
+  float bss_phase_ms[4] = {};  // phases of the last timed pbbss_bss_eval (pbbss_bss_eval_phase_ms)
 };
 
 namespace pbbss {
@@ -63,20 +65,6 @@ inline bool embed_shape_ok(int64_t B, int64_t N, int E, int K) {
   return B >= 1 && B <= 65535 && N >= 1 && E >= 1 && E <= kEmbedMaxE && K >= 1 &&
          K <= kEmbedWideMaxK;
 }
-
-// Bump allocator over a slab (256-byte aligned pieces).  Without a base it only measures: take()
-// counts the bytes and hands out null.
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b = nullptr) : base(static_cast<char*>(b)) {}
-  template <typename T>
-  T* take(size_t count) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += (count * sizeof(T) + 255) & ~(size_t)255;
-    return p;
-  }
-};
 
 // Carve a workspace out of `slab`.  `pieces(Carver&)` lists the take() calls ONCE; it runs on a
 // measuring carver, the slab grows to that count, and it runs again on the slab -- so the bytes

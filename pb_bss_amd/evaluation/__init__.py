@@ -1,10 +1,13 @@
-"""Drop-in for the NumPy part of pb_bss.evaluation (reference: pb_bss/evaluation/__init__.py):
-`si_sdr` and the `sxr_module` (`get_snr`, `set_snr`, `input_sxr`, `output_sxr`) on the device.
+"""Drop-in for pb_bss.evaluation (reference: pb_bss/evaluation/__init__.py) on the device:
+`si_sdr`, the `sxr_module` (`get_snr`, `set_snr`, `input_sxr`, `output_sxr`), the BSS-Eval
+metrics `mir_eval_sources` (SDR / SIR / SAR, computed here without the `mir_eval` package) and
+the `InputMetrics` / `OutputMetrics` classes on top of them.
 
-The reference's other metrics (`mir_eval_sources`, `pesq`, `stoi`, `srmr`) and the
-`InputMetrics` / `OutputMetrics` classes on top of them wrap third-party packages and are not
-provided."""
+The reference's `pesq`, `stoi` and `srmr` wrap third-party packages and are not provided; the
+two classes list them as disabled and raise NotImplementedError for them."""
 from . import sxr_module
+from .module_mir_eval import mir_eval_sources
 from .module_si_sdr import si_sdr
+from .wrapper import InputMetrics, OutputMetrics
 
-__all__ = ['si_sdr', 'sxr_module']
+__all__ = ['si_sdr', 'sxr_module', 'mir_eval_sources', 'InputMetrics', 'OutputMetrics']
