@@ -1085,6 +1085,39 @@ int pbbss_kmeans_plusplus(pbbss_handle_t h, const void* y, int y_is_f64, int64_t
                           void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* (X)  Gammatone filterbank and SRMR (reference: transform/gammatone.py,        */
+/* evaluation/module_srmr.py), float64.  Rows are float32 or float64 (is_f64),   */
+/* contiguous (rows, N), widened at the load.  After the voice activity          */
+/* detection the rows of one call differ in length: they stay in (rows, N)       */
+/* buffers with a device array of lengths; `lengths` NULL means N for every row. */
+/* Every biquad is five doubles b0 b1 b2 a1 a2 (a0 = 1), computed by the host.   */
+/*                                                                               */
+/* pbbss_srmr_vad: per row, drops the samples strictly between two neighbouring  */
+/* samples with |x| > max|x|^2 / 1e5 that lie more than 0.05 sample_rate apart,  */
+/* then subtracts the mean and divides by the population standard deviation.     */
+/* out (rows, N) float64, zeros beyond out_lengths[row]; an all-zero row is NaN. */
+/* pbbss_gammatone: n channels of four cascaded biquads, coef (n, 4, 5), out     */
+/* (n, rows, N), zeros beyond a row's length.                                    */
+/* pbbss_srmr_energies: analytic (n, rows, N) complex128; modulus, the eight     */
+/* modulation biquads coef (8, 5), and the mean over the zero-padded Hamming     */
+/* frames (int(sample_rate / 1000) * 256 long, a quarter of that apart) of the   */
+/* squared sum: out_means (rows, n, 8).                                          */
+/* pbbss_srmr_score: the 90 % bandwidth rule and the energy ratio per row, from  */
+/* erbs (n) and cutoffs (8).                                                     */
+/* PBBSS_ERR_UNSUPPORTED: n outside 1..64, N > 2^24, more than 65535 rows,       */
+/* sample_rate < 1000.  PBBSS_ERR_INVALID_ARG: null pointers, sizes < 1.         */
+/* ------------------------------------------------------------------------- */
+int pbbss_srmr_vad(pbbss_handle_t h, const void* x, int is_f64, int64_t rows, int64_t N,
+                   int sample_rate, double* out, int32_t* out_lengths, void* stream);
+int pbbss_gammatone(pbbss_handle_t h, const void* x, int is_f64, int64_t rows, int64_t N,
+                    const int32_t* lengths, int n, const double* coef, double* out, void* stream);
+int pbbss_srmr_energies(pbbss_handle_t h, const void* analytic, int64_t rows, int64_t N,
+                        const int32_t* lengths, int n, int sample_rate, const double* coef,
+                        double* out_means, void* stream);
+int pbbss_srmr_score(pbbss_handle_t h, const double* means, int64_t rows, int n,
+                     const double* erbs, const double* cutoffs, double* out, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Timing hook for bench.py: runs `fit` with HIP events recorded on `stream`   */
 /* around the EM kernel launch(es) only and returns the elapsed milliseconds   */
 /* of the most recent call (the roofline figure needs the kernel duration on   */

@@ -247,6 +247,10 @@ SIGNATURES = {
         vp],
     'pbbss_kmeans_predict': [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp],
     'pbbss_kmeans_plusplus': [vp, vp, i32, i64, i64, i32, i32, vp, i32, vp, vp, vp, vp],
+    'pbbss_srmr_vad': [vp, vp, i32, i64, i64, i32, vp, vp, vp],
+    'pbbss_gammatone': [vp, vp, i32, i64, i64, vp, i32, vp, vp, vp],
+    'pbbss_srmr_energies': [vp, vp, i64, i64, vp, i32, i32, vp, vp, vp],
+    'pbbss_srmr_score': [vp, vp, i64, i32, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 

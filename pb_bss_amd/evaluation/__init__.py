@@ -1,13 +1,15 @@
 """Drop-in for pb_bss.evaluation (reference: pb_bss/evaluation/__init__.py) on the device:
 `si_sdr`, the `sxr_module` (`get_snr`, `set_snr`, `input_sxr`, `output_sxr`), the BSS-Eval
-metrics `mir_eval_sources` (SDR / SIR / SAR, computed here without the `mir_eval` package) and
-the `InputMetrics` / `OutputMetrics` classes on top of them.
+metrics `mir_eval_sources` (SDR / SIR / SAR, computed here without the `mir_eval` package),
+`srmr` (the reference's own NumPy / SciPy code, restated for the device; it needs no clean
+source) and the `InputMetrics` / `OutputMetrics` classes.
 
-The reference's `pesq`, `stoi` and `srmr` wrap third-party packages and are not provided; the
-two classes list them as disabled and raise NotImplementedError for them."""
+The reference's `pesq` and `stoi` wrap third-party packages and are not provided.  The two
+classes list them, and for now `srmr` too, as disabled and raise NotImplementedError for them."""
 from . import sxr_module
 from .module_mir_eval import mir_eval_sources
 from .module_si_sdr import si_sdr
+from .module_srmr import srmr
 from .wrapper import InputMetrics, OutputMetrics
 
-__all__ = ['si_sdr', 'sxr_module', 'mir_eval_sources', 'InputMetrics', 'OutputMetrics']
+__all__ = ['si_sdr', 'sxr_module', 'mir_eval_sources', 'srmr', 'InputMetrics', 'OutputMetrics']

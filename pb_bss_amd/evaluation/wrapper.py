@@ -2,10 +2,11 @@
 every metric of one utterance behind one object, each computed on first use and kept.
 
 The metrics this package computes on the device are there: BSS-Eval (`mir_eval_sdr`, `_sir`,
-`_sar`, `_selection`), `si_sdr` and the invasive SxR.  `pesq`, `stoi` and `srmr` wrap
-third-party packages that are not available; they raise NotImplementedError and are listed as
-disabled instead of available.  Arrays go in as NumPy arrays or device tensors and the metrics
-come back in kind.
+`_sar`, `_selection`), `si_sdr` and the invasive SxR.  `pesq` and `stoi` wrap third-party
+packages that are not available; they raise NotImplementedError and are listed as disabled
+instead of available.  So does `srmr` here, for now: the package computes it
+(`pb_bss_amd.evaluation.srmr`, which needs no clean source), the two classes are not wired to it
+yet.  Arrays go in as NumPy arrays or device tensors and the metrics come back in kind.
 
 Both classes are thin: `_Metrics` holds the table of metric names, the dict views and the
 properties that only pick a key out of a grouped result; a subclass says which signals it got,
