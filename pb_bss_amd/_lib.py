@@ -3,6 +3,11 @@
 The product path has NO CPU fallback: if the shared library is missing or a
 call fails this module raises.  PyTorch-ROCm is used only as the owner of
 device memory and streams; all arithmetic happens inside the HIP library.
+
+The calling convention of the header lives here, once: SIGNATURES describes every export as
+data, `launch` (handle first, stream last) and `control` (handle, no stream) marshal a call from
+it.  The modules of the package name the export and hand over tensors and numbers; only the few
+host functions without a handle are called on `load()` directly.
 """
 import ctypes
 import os
@@ -317,6 +322,10 @@ def require_gpu():
 
 def handle(device_index=None):
     """One C handle per (device, host thread)."""
+    if device_index is not None:  # the per-call path: no GPU query, no lock once it exists
+        h = _handles.get((device_index, threading.get_ident()))
+        if h is not None:
+            return h
     t = require_gpu()
     if device_index is None:
         device_index = t.cuda.current_device()
@@ -337,12 +346,73 @@ def stream_ptr(device_index=None):
     return ctypes.c_void_p(t.cuda.current_stream(device_index).cuda_stream)
 
 
+_CTYPES_POINTERS = (ctypes._SimpleCData, ctypes.Array, bytes)  # c_void_p, arrays, string buffers
+
+
 def ptr(tensor):
-    """Device pointer of a contiguous torch tensor (None -> NULL)."""
-    if tensor is None:
-        return None
+    """Device pointer of a contiguous torch tensor (None -> NULL); what already is a ctypes
+    pointer argument passes through."""
+    if tensor is None or isinstance(tensor, _CTYPES_POINTERS):
+        return tensor
     assert tensor.is_cuda and tensor.is_contiguous(), (tensor.device, tensor.stride())
     return ctypes.c_void_p(tensor.data_ptr())
+
+
+def view_ptr(tensor):
+    """Device pointer of a (possibly strided) view; the strides travel separately."""
+    assert tensor.is_cuda, tensor.device
+    return ctypes.c_void_p(tensor.data_ptr())
+
+
+# ---- the calling convention ---------------------------------------------------------------------
+def _ref(a):
+    """POINTER(T) slot: a Structure or a scalar ctypes object goes by reference, an array as it
+    is."""
+    return ctypes.byref(a) if isinstance(a, (ctypes.Structure, ctypes._SimpleCData)) else a
+
+
+# export -> one converter per parameter behind the handle (the stream's included where there is
+# one): pure data from SIGNATURES, so that a call is one zip over its arguments
+_CONVERTERS = {
+    name: tuple(ptr if c is vp else float if c is dbl else int if c in (i32, u32, i64) else _ref
+                for c in argtypes[1:])
+    for name, argtypes in SIGNATURES.items() if argtypes and argtypes[0] is vp}
+
+
+def _index(device):
+    return device if device is None or isinstance(device, int) else device.index
+
+
+def _marshal(name, converters, expected, args):
+    if len(args) != expected:
+        raise TypeError(f'{name} takes {expected} arguments behind the handle, got {len(args)}')
+    return [c(a) for c, a in zip(converters, args)]
+
+
+def launch(name, device, *args, what=None, accept=()):
+    """Call an export whose first parameter is the handle and whose last is the stream: this
+    thread's handle of `device` (a torch.device or an index), `args` marshalled slot by slot from
+    SIGNATURES[name] (pointer slots: None, a contiguous device tensor or a ctypes object; option
+    structs by reference; scalars through int() / float()), the current torch stream of the device
+    read now.  Raises through check(rc, what or name) unless rc is in `accept`; returns rc."""
+    index = _index(device)
+    converters = _CONVERTERS[name]
+    argv = _marshal(name, converters, len(converters) - 1, args)
+    rc = getattr(load(), name)(handle(index), *argv, stream_ptr(index))
+    if rc != OK and rc not in accept:
+        check(rc, what or name)
+    return rc
+
+
+def control(name, device_index, *args, what=None):
+    """As launch, for the exports that take the handle but no stream (settings, read-outs, the
+    communicator)."""
+    converters = _CONVERTERS[name]
+    argv = _marshal(name, converters, len(converters), args)
+    rc = getattr(load(), name)(handle(_index(device_index)), *argv)
+    if rc != OK:
+        check(rc, what or name)
+    return rc
 
 
 # ---- host <-> device plumbing ---------------------------------------------------

@@ -106,19 +106,17 @@ def _too_few(n_samples, n_clusters):
 def _call_fit(xd, K, sal, centers, max_iter, tol, block):
     t = _lib.torch()
     B, N, E = xd.shape
-    dev = xd.device.index
     out_c = t.empty((B, K, E), dtype=t.float64, device=xd.device)
     labels = t.empty((B, N), dtype=t.int32, device=xd.device)
     inertia = t.empty((B,), dtype=t.float64, device=xd.device)
     n_iter = t.empty((B,), dtype=t.int32, device=xd.device)
-    rc = _lib.load().pbbss_kmeans_fit(
-        _lib.handle(dev), _lib.ptr(xd), int(xd.dtype == t.float64), B, N, E, K, _lib.ptr(sal),
-        _lib.ptr(centers), int(max_iter), float(tol), int(block), _lib.ptr(out_c),
-        _lib.ptr(labels), _lib.ptr(inertia), _lib.ptr(n_iter), _lib.stream_ptr(dev))
-    if rc == _lib.ERR_INVALID_ARG and sal is not None:
+    rc = _lib.launch('pbbss_kmeans_fit', xd.device, xd, xd.dtype == t.float64, B, N, E, K, sal,
+                     centers, max_iter, tol, block, out_c, labels, inertia, n_iter,
+                     what=f'kmeans_fit(B={B}, N={N}, E={E}, K={K})',
+                     accept=() if sal is None else (_lib.ERR_INVALID_ARG,))
+    if rc == _lib.ERR_INVALID_ARG:
         # every other argument was validated here: a problem selects fewer rows than classes
         raise _too_few('(selected rows)', K)
-    _lib.check(rc, f'kmeans_fit(B={B}, N={N}, E={E}, K={K})')
     return out_c, labels, inertia, n_iter
 
 
@@ -126,28 +124,23 @@ def _call_predict(xd, centers, one_hot=False, inertia=False):
     t = _lib.torch()
     B, N, E = xd.shape
     K = centers.shape[1]
-    dev = xd.device.index
     labels = t.empty((B, N), dtype=t.int32, device=xd.device)
     hot = t.empty((B, K, N), dtype=xd.dtype, device=xd.device) if one_hot else None
     val = t.empty((B,), dtype=t.float64, device=xd.device) if inertia else None
-    rc = _lib.load().pbbss_kmeans_predict(
-        _lib.handle(dev), _lib.ptr(xd), int(xd.dtype == t.float64), B, N, E, K,
-        _lib.ptr(centers), _lib.ptr(labels), _lib.ptr(hot), _lib.ptr(val), _lib.stream_ptr(dev))
-    _lib.check(rc, f'kmeans_predict(B={B}, N={N}, E={E}, K={K})')
+    _lib.launch('pbbss_kmeans_predict', xd.device, xd, xd.dtype == t.float64, B, N, E, K, centers,
+                labels, hot, val, what=f'kmeans_predict(B={B}, N={N}, E={E}, K={K})')
     return labels, hot, val
 
 
 def _call_plusplus(xd, K, sal, randoms, trials):
     t = _lib.torch()
     B, N, E = xd.shape
-    dev = xd.device.index
     rnd = t.from_numpy(np.ascontiguousarray(randoms, np.float64)).to(xd.device)
     indices = t.empty((B, K), dtype=t.int32, device=xd.device)
     centers = t.empty((B, K, E), dtype=t.float64, device=xd.device)
-    rc = _lib.load().pbbss_kmeans_plusplus(
-        _lib.handle(dev), _lib.ptr(xd), int(xd.dtype == t.float64), B, N, E, K, _lib.ptr(sal),
-        int(trials), _lib.ptr(rnd), _lib.ptr(indices), _lib.ptr(centers), _lib.stream_ptr(dev))
-    _lib.check(rc, f'kmeans_plusplus(B={B}, N={N}, E={E}, K={K})')
+    _lib.launch('pbbss_kmeans_plusplus', xd.device, xd, xd.dtype == t.float64, B, N, E, K, sal,
+                trials, rnd, indices, centers,
+                what=f'kmeans_plusplus(B={B}, N={N}, E={E}, K={K})')
     return indices, centers
 
 

@@ -1,12 +1,16 @@
-"""Thin device-tensor layer over the C ABI: every function takes/returns
-contiguous torch CUDA tensors with the independent axes flattened to one batch
-axis B, launches exactly the library call named in its docstring on the current
-torch stream, and raises the reference's exception types from status words.
+"""Thin device-tensor layer over the C ABI for the mixture models, the beamformers, permutation
+alignment and the STFT (the masks, the evaluation metrics, k-means and the gammatone filterbank
+bind their exports in their own modules): every function takes/returns contiguous torch CUDA
+tensors with the independent axes flattened to one batch axis B, launches exactly the library
+call named in its docstring on the current torch stream, and raises the reference's exception
+types from status words.
 
-No arithmetic is done here beyond shape bookkeeping.
+No arithmetic is done here beyond shape bookkeeping, and no marshalling either: handle, stream,
+pointers, scalar conversion and the return-code check are `_lib.launch` / `_lib.control`.
 """
 import ctypes
 import os
+import threading
 
 import numpy as np
 
@@ -15,6 +19,10 @@ from . import _lib
 
 def _t():
     return _lib.torch()
+
+
+# launch(..., accept=_NOT_SERVED): PBBSS_ERR_UNSUPPORTED is an answer of the call, not an error
+_NOT_SERVED = (_lib.ERR_UNSUPPORTED,)
 
 
 def _status_bits(status):
@@ -107,11 +115,28 @@ def normalize_observation(y):
     B, T, D = y.shape
     is128 = y.dtype == t.complex128
     out = t.empty((B, D, T), dtype=y.dtype, device=y.device)
-    rc = _lib.load().pbbss_normalize_observation(
-        _lib.handle(y.device.index), _lib.ptr(y), int(is128), B, T, D,
-        _lib.ptr(out), _lib.stream_ptr(y.device.index))
-    _lib.check(rc, 'normalize_observation')
+    _lib.launch('pbbss_normalize_observation', y.device, y, is128, B, T, D, out,
+                what='normalize_observation')
     return out
+
+
+def _btd(y, layout):
+    """(B, T, D) of an observation in `layout`"""
+    if layout == _lib.LAYOUT_TD:
+        B, T, D = y.shape
+    else:
+        B, D, T = y.shape
+    return B, T, D
+
+
+def _check_em_inputs(t, model, gamma0, saliency, activity, B, K, T):
+    """gamma0 (read only without a start model), saliency and activity of the cACGMM fits"""
+    if model is None:
+        assert gamma0.shape == (B, K, T) and gamma0.dtype == t.float64, (gamma0.shape, gamma0.dtype)
+    if saliency is not None:
+        assert saliency.shape == (B, T) and saliency.dtype == t.float64
+    if activity is not None:
+        assert activity.shape == (B, K, T) and activity.dtype == t.uint8
 
 
 def em_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None,
@@ -128,10 +153,7 @@ def em_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None,
     """
     t = _t()
     dev = y.device
-    if layout == _lib.LAYOUT_TD:
-        B, T, D = y.shape
-    else:
-        B, D, T = y.shape
+    B, T, D = _btd(y, layout)
     is128 = y.dtype == t.complex128
     assert y.dtype in (t.complex64, t.complex128), y.dtype
     opts = _lib.EmOpts(
@@ -148,11 +170,7 @@ def em_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None,
         assert in_vec.shape == (B, K, D, D) and in_val.shape == (B, K, D) and in_w.shape == (B, K)
     else:
         in_vec = in_val = in_w = None
-        assert gamma0.shape == (B, K, T) and gamma0.dtype == f64, (gamma0.shape, gamma0.dtype)
-    if saliency is not None:
-        assert saliency.shape == (B, T) and saliency.dtype == f64
-    if activity is not None:
-        assert activity.shape == (B, K, T) and activity.dtype == t.uint8
+    _check_em_inputs(t, model, gamma0, saliency, activity, B, K, T)
 
     def launch():
         out_vec = t.empty((B, K, D, D), dtype=t.complex128, device=dev)
@@ -161,13 +179,9 @@ def em_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None,
         out_st = t.empty((B, K), dtype=t.int32, device=dev)  # every row is written by the library
         out_aff = t.empty((B, K, T), dtype=f64, device=dev) if final_predict else None
         out_q = t.empty((B, K, T), dtype=f64, device=dev) if (final_predict and return_q) else None
-        rc = _lib.load().pbbss_cacgmm_fit(
-            _lib.handle(dev.index), _lib.ptr(y), B, T, D, K, _lib.ptr(gamma0),
-            _lib.ptr(in_vec), _lib.ptr(in_val), _lib.ptr(in_w), _lib.ptr(saliency),
-            _lib.ptr(activity), ctypes.byref(opts), _lib.ptr(out_vec),
-            _lib.ptr(out_val), _lib.ptr(out_w), _lib.ptr(out_st), _lib.ptr(out_aff),
-            _lib.ptr(out_q), _lib.stream_ptr(dev.index))
-        _lib.check(rc, f'cacgmm_fit(B={B},T={T},D={D},K={K})')
+        _lib.launch('pbbss_cacgmm_fit', dev, y, B, T, D, K, gamma0, in_vec, in_val, in_w,
+                    saliency, activity, opts, out_vec, out_val, out_w, out_st, out_aff, out_q,
+                    what=f'cacgmm_fit(B={B},T={T},D={D},K={K})')
         return dict(eigvec=out_vec, eigval=out_val, weight=out_w, status=out_st,
                     affiliation=out_aff, quadratic_form=out_q)
 
@@ -215,20 +229,13 @@ def em_fit_shared(y, K, group, *, weight_mode, gamma0=None, model=None, iteratio
         assert tuple(in_w.shape) == wshape and in_w.is_contiguous(), (in_w.shape, wshape)
     else:
         in_vec = in_val = in_w = None
-        assert gamma0.shape == (B, K, T) and gamma0.dtype == f64, (gamma0.shape, gamma0.dtype)
-    if saliency is not None:
-        assert saliency.shape == (B, T) and saliency.dtype == f64
-    if activity is not None:
-        assert activity.shape == (B, K, T) and activity.dtype == t.uint8
-    rc = _lib.load().pbbss_cacgmm_fit_shared(
-        _lib.handle(dev.index), _lib.ptr(y), B, T, D, K, int(group), _lib.ptr(gamma0),
-        _lib.ptr(in_vec), _lib.ptr(in_val), _lib.ptr(in_w), _lib.ptr(saliency),
-        _lib.ptr(activity), ctypes.byref(opts), _lib.ptr(out_vec),
-        _lib.ptr(out_val), _lib.ptr(out_w), _lib.ptr(out_st), _lib.ptr(out_aff),
-        _lib.ptr(out_q), _lib.stream_ptr(dev.index))
+    _check_em_inputs(t, model, gamma0, saliency, activity, B, K, T)
+    rc = _lib.launch('pbbss_cacgmm_fit_shared', dev, y, B, T, D, K, group, gamma0, in_vec, in_val,
+                     in_w, saliency, activity, opts, out_vec, out_val, out_w, out_st, out_aff,
+                     out_q, what=f'cacgmm_fit_shared(B={B},group={group},T={T},D={D},K={K})',
+                     accept=_NOT_SERVED)
     if rc == _lib.ERR_UNSUPPORTED:
         return None
-    _lib.check(rc, f'cacgmm_fit_shared(B={B},group={group},T={T},D={D},K={K})')
     if check_status:
         if iterations > 0 and _cooperative_timed_out(out_st, dev):
             return None
@@ -243,10 +250,7 @@ def em_predict(y, eigvec, eigval, weight, *, activity=None,
     """pbbss_cacgmm_predict.  weight is (B,K) or (B,K,T) f64."""
     t = _t()
     dev = y.device
-    if layout == _lib.LAYOUT_TD:
-        B, T, D = y.shape
-    else:
-        B, D, T = y.shape
+    B, T, D = _btd(y, layout)
     K = eigvec.shape[1]
     is128 = y.dtype == t.complex128
     f64 = t.float64
@@ -258,12 +262,9 @@ def em_predict(y, eigvec, eigval, weight, *, activity=None,
     aff = t.empty((B, K, T), dtype=f64, device=dev) if want_affiliation else None
     q = t.empty((B, K, T), dtype=f64, device=dev) if want_q else None
     lp = t.empty((B, K, T), dtype=f64, device=dev) if want_log_pdf else None
-    rc = _lib.load().pbbss_cacgmm_predict(
-        _lib.handle(dev.index), _lib.ptr(y), B, T, D, K, _lib.ptr(eigvec),
-        _lib.ptr(eigval), _lib.ptr(weight), wb, wk, wt, _lib.ptr(activity),
-        int(layout), int(is128), float(affiliation_eps), _lib.ptr(aff),
-        _lib.ptr(q), _lib.ptr(lp), _lib.stream_ptr(dev.index))
-    _lib.check(rc, f'cacgmm_predict(B={B},T={T},D={D},K={K})')
+    _lib.launch('pbbss_cacgmm_predict', dev, y, B, T, D, K, eigvec, eigval, weight, wb, wk, wt,
+                activity, layout, is128, affiliation_eps, aff, q, lp,
+                what=f'cacgmm_predict(B={B},T={T},D={D},K={K})')
     return aff, q, lp
 
 
@@ -273,10 +274,7 @@ def cacg_m_step(y, saliency, quadratic_form, *, layout=_lib.LAYOUT_DT,
     """pbbss_cacg_m_step: saliency/quadratic_form (B,K,T) f64."""
     t = _t()
     dev = y.device
-    if layout == _lib.LAYOUT_TD:
-        B, T, D = y.shape
-    else:
-        B, D, T = y.shape
+    B, T, D = _btd(y, layout)
     K = saliency.shape[1]
     is128 = y.dtype == t.complex128
 
@@ -285,13 +283,9 @@ def cacg_m_step(y, saliency, quadratic_form, *, layout=_lib.LAYOUT_DT,
         out_val = t.empty((B, K, D), dtype=t.float64, device=dev)
         out_st = t.zeros((B, K), dtype=t.int32, device=dev)
         out_cov = t.empty((B, K, D, D), dtype=t.complex128, device=dev) if want_cov else None
-        rc = _lib.load().pbbss_cacg_m_step(
-            _lib.handle(dev.index), _lib.ptr(y), B, T, D, K, _lib.ptr(saliency),
-            _lib.ptr(quadratic_form), int(layout), int(is128),
-            _lib.COVNORM[covariance_norm], float(eigenvalue_floor),
-            _lib.ptr(out_vec), _lib.ptr(out_val), _lib.ptr(out_cov),
-            _lib.ptr(out_st), _lib.stream_ptr(dev.index))
-        _lib.check(rc, f'cacg_m_step(B={B},T={T},D={D},K={K})')
+        _lib.launch('pbbss_cacg_m_step', dev, y, B, T, D, K, saliency, quadratic_form, layout,
+                    is128, _lib.COVNORM[covariance_norm], eigenvalue_floor, out_vec, out_val,
+                    out_cov, out_st, what=f'cacg_m_step(B={B},T={T},D={D},K={K})')
         return dict(eigvec=out_vec, eigval=out_val, cov=out_cov, status=out_st)
 
     # ONE iteration of the EM kernel: split groups need kSplitMinIterations = 3 (em_launch.hpp), so
@@ -309,10 +303,7 @@ def heev(a):
     val = t.empty((N, D), dtype=t.float64, device=a.device)
     vec = t.empty((N, D, D), dtype=t.complex128, device=a.device)
     st = t.zeros((N,), dtype=t.int32, device=a.device)
-    rc = _lib.load().pbbss_heev_batched(
-        _lib.handle(a.device.index), _lib.ptr(a), N, D, _lib.ptr(val),
-        _lib.ptr(vec), _lib.ptr(st), _lib.stream_ptr(a.device.index))
-    _lib.check(rc, f'heev(N={N},D={D})')
+    _lib.launch('pbbss_heev_batched', a.device, a, N, D, val, vec, st, what=f'heev(N={N},D={D})')
     return val, vec, st
 
 
@@ -322,11 +313,8 @@ def psd(x, mask, normalize=True):
     B, D, T = x.shape
     K = 1 if mask is None else mask.shape[1]
     out = t.empty((B, K, D, D), dtype=t.complex128, device=x.device)
-    rc = _lib.load().pbbss_psd(
-        _lib.handle(x.device.index), _lib.ptr(x), int(x.dtype == t.complex128),
-        B, T, D, K, _lib.ptr(mask), int(bool(normalize)), _lib.ptr(out),
-        _lib.stream_ptr(x.device.index))
-    _lib.check(rc, f'psd(B={B},T={T},D={D},K={K})')
+    _lib.launch('pbbss_psd', x.device, x, x.dtype == t.complex128, B, T, D, K, mask,
+                bool(normalize), out, what=f'psd(B={B},T={T},D={D},K={K})')
     return out
 
 
@@ -336,10 +324,7 @@ def gev(target, noise):
     N, D, _ = target.shape
     w = t.empty((N, D), dtype=t.complex128, device=target.device)
     st = t.zeros((N,), dtype=t.int32, device=target.device)
-    rc = _lib.load().pbbss_gev(
-        _lib.handle(target.device.index), _lib.ptr(target), _lib.ptr(noise), N,
-        D, _lib.ptr(w), _lib.ptr(st), _lib.stream_ptr(target.device.index))
-    _lib.check(rc, f'gev(N={N},D={D})')
+    _lib.launch('pbbss_gev', target.device, target, noise, N, D, w, st, what=f'gev(N={N},D={D})')
     return w, st
 
 
@@ -351,11 +336,8 @@ def gev_general(target, noise, want_eigenvalue=False):
     w = t.empty((N, D), dtype=t.complex128, device=target.device)
     lam = t.empty((N,), dtype=t.complex128, device=target.device) if want_eigenvalue else None
     st = t.zeros((N,), dtype=t.int32, device=target.device)
-    rc = _lib.load().pbbss_gev_general(
-        _lib.handle(target.device.index), _lib.ptr(target), _lib.ptr(noise), N, D, _lib.ptr(w),
-        _lib.ptr(lam) if lam is not None else None, _lib.ptr(st),
-        _lib.stream_ptr(target.device.index))
-    _lib.check(rc, f'gev_general(N={N},D={D})')
+    _lib.launch('pbbss_gev_general', target.device, target, noise, N, D, w, lam, st,
+                what=f'gev_general(N={N},D={D})')
     return w, lam, st
 
 
@@ -366,10 +348,7 @@ def solve(A, Bm):
     M = Bm.shape[-1]
     x = t.empty((N, D, M), dtype=t.complex128, device=A.device)
     st = t.zeros((N,), dtype=t.int32, device=A.device)
-    rc = _lib.load().pbbss_solve(
-        _lib.handle(A.device.index), _lib.ptr(A), _lib.ptr(Bm), N, D, M,
-        _lib.ptr(x), _lib.ptr(st), _lib.stream_ptr(A.device.index))
-    _lib.check(rc, f'solve(N={N},D={D},M={M})')
+    _lib.launch('pbbss_solve', A.device, A, Bm, N, D, M, x, st, what=f'solve(N={N},D={D},M={M})')
     return x, st
 
 
@@ -382,11 +361,8 @@ def mvdr_souden(target, noise, eps):
     den = t.empty((N, D), dtype=t.complex128, device=target.device)
     # the fused kernels (D <= 8) write every status word; no fill launch in front of them
     st = (t.empty if D <= 8 else t.zeros)((N,), dtype=t.int32, device=target.device)
-    rc = _lib.load().pbbss_mvdr_souden(
-        _lib.handle(target.device.index), _lib.ptr(target), _lib.ptr(noise), N,
-        D, float(eps), _lib.ptr(mat), _lib.ptr(num), _lib.ptr(den), _lib.ptr(st),
-        _lib.stream_ptr(target.device.index))
-    _lib.check(rc, f'mvdr_souden(N={N},D={D})')
+    _lib.launch('pbbss_mvdr_souden', target.device, target, noise, N, D, eps, mat, num, den, st,
+                what=f'mvdr_souden(N={N},D={D})')
     return mat, num, den, st
 
 
@@ -401,11 +377,9 @@ def select_reference_channel(mat, num, den, L, F, eps, lead_stride=None, bin_str
     w = t.empty((L, F, D), dtype=t.complex128, device=mat.device)
     ref = t.empty((L,), dtype=t.int32, device=mat.device)
     ok = t.empty((L,), dtype=t.int32, device=mat.device)
-    rc = _lib.load().pbbss_select_reference_channel(
-        _lib.handle(mat.device.index), _lib.ptr(mat), _lib.ptr(num), _lib.ptr(den), int(L), int(F),
-        int(D), int(F if lead_stride is None else lead_stride), int(bin_stride), float(eps),
-        _lib.ptr(w), _lib.ptr(ref), _lib.ptr(ok), _lib.stream_ptr(mat.device.index))
-    _lib.check(rc, f'select_reference_channel(L={L},F={F},D={D})')
+    _lib.launch('pbbss_select_reference_channel', mat.device, mat, num, den, L, F, D,
+                F if lead_stride is None else lead_stride, bin_stride, eps, w, ref, ok,
+                what=f'select_reference_channel(L={L},F={F},D={D})')
     return w, ref, ok
 
 
@@ -415,10 +389,7 @@ def mvdr(atf, noise):
     N, D = atf.shape
     w = t.empty((N, D), dtype=t.complex128, device=atf.device)
     st = t.zeros((N,), dtype=t.int32, device=atf.device)
-    rc = _lib.load().pbbss_mvdr(
-        _lib.handle(atf.device.index), _lib.ptr(atf), _lib.ptr(noise), N, D,
-        _lib.ptr(w), _lib.ptr(st), _lib.stream_ptr(atf.device.index))
-    _lib.check(rc, f'mvdr(N={N},D={D})')
+    _lib.launch('pbbss_mvdr', atf.device, atf, noise, N, D, w, st, what=f'mvdr(N={N},D={D})')
     return w, st
 
 
@@ -427,10 +398,7 @@ def ban(w, noise):
     t = _t()
     N, D = w.shape
     out = t.empty((N, D), dtype=t.complex128, device=w.device)
-    rc = _lib.load().pbbss_ban(
-        _lib.handle(w.device.index), _lib.ptr(w), _lib.ptr(noise), N, D,
-        _lib.ptr(out), _lib.stream_ptr(w.device.index))
-    _lib.check(rc, f'ban(N={N},D={D})')
+    _lib.launch('pbbss_ban', w.device, w, noise, N, D, out, what=f'ban(N={N},D={D})')
     return out
 
 
@@ -442,22 +410,18 @@ def apply_bf(w, x):
     Bx, D, T = x.shape
     B = w.shape[0]
     out = t.empty((B, T), dtype=t.complex128, device=x.device)
+    what = f'apply_beamforming_vector(B={B},Bx={Bx},T={T},D={D})'
     if B == Bx:
-        rc = _lib.load().pbbss_apply_beamforming_vector(
-            _lib.handle(x.device.index), _lib.ptr(w), _lib.ptr(x),
-            int(x.dtype == t.complex128), B, T, D, _lib.ptr(out),
-            _lib.stream_ptr(x.device.index))
+        _lib.launch('pbbss_apply_beamforming_vector', x.device, w, x, x.dtype == t.complex128,
+                    B, T, D, out, what=what)
     else:
-        rc = _lib.load().pbbss_apply_beamforming_vector_shared(
-            _lib.handle(x.device.index), _lib.ptr(w), _lib.ptr(x),
-            int(x.dtype == t.complex128), B, Bx, T, D, _lib.ptr(out),
-            _lib.stream_ptr(x.device.index))
-    _lib.check(rc, f'apply_beamforming_vector(B={B},Bx={Bx},T={T},D={D})')
+        _lib.launch('pbbss_apply_beamforming_vector_shared', x.device, w, x,
+                    x.dtype == t.complex128, B, Bx, T, D, out, what=what)
     return out
 
 
 def set_timing(enable, device_index=None):
-    _lib.check(_lib.load().pbbss_set_timing(_lib.handle(device_index), int(enable)), 'set_timing')
+    _lib.control('pbbss_set_timing', device_index, enable, what='set_timing')
 
 
 def last_kernel_ms(device_index=None, lag=0):
@@ -465,9 +429,11 @@ def last_kernel_ms(device_index=None, lag=0):
     with lag = 2 inside a loop of launches, the queue keeps two launches behind the running one
     (pbbss_kernel_ms_lagged)."""
     ms = ctypes.c_float()
-    _lib.check(_lib.load().pbbss_kernel_ms_lagged(_lib.handle(device_index), int(lag),
-                                                  ctypes.byref(ms)), 'kernel_ms_lagged')
+    _lib.control('pbbss_kernel_ms_lagged', device_index, lag, ms, what='kernel_ms_lagged')
     return float(ms.value)
+
+
+PA_METRIC = {'cos': 0, 'multiply': 1, 'euclidean': 2}
 
 
 def dhtv_calculate_mapping(mask, plan, optimal=False, metric='cos'):
@@ -478,11 +444,9 @@ def dhtv_calculate_mapping(mask, plan, optimal=False, metric='cos'):
     feat = t.empty_like(mask)
     mapping = t.empty((U, K, F), dtype=t.int32, device=mask.device)
     st = t.zeros((U,), dtype=t.int32, device=mask.device)
-    rc = _lib.load().pbbss_dhtv_calculate_mapping(
-        _lib.handle(mask.device.index), _lib.ptr(mask), U, K, F, T, _lib.ptr(plan),
-        int(plan.shape[0]), int(bool(optimal)), PA_METRIC[metric], _lib.ptr(feat), _lib.ptr(mapping),
-        _lib.ptr(st), _lib.stream_ptr(mask.device.index))
-    _lib.check(rc, f'dhtv_calculate_mapping(U={U},K={K},F={F},T={T})')
+    _lib.launch('pbbss_dhtv_calculate_mapping', mask.device, mask, U, K, F, T, plan,
+                plan.shape[0], bool(optimal), PA_METRIC[metric], feat, mapping, st,
+                what=f'dhtv_calculate_mapping(U={U},K={K},F={F},T={T})')
     return mapping, feat, st
 
 
@@ -491,26 +455,15 @@ def apply_mapping(mask, mapping):
     t = _t()
     U, K, F, T = mask.shape
     out = t.empty_like(mask)
-    rc = _lib.load().pbbss_apply_mapping(
-        _lib.handle(mask.device.index), _lib.ptr(mask), _lib.ptr(mapping), U, K, F, T,
-        _lib.ptr(out), _lib.stream_ptr(mask.device.index))
-    _lib.check(rc, f'apply_mapping(U={U},K={K},F={F},T={T})')
+    _lib.launch('pbbss_apply_mapping', mask.device, mask, mapping, U, K, F, T, out,
+                what=f'apply_mapping(U={U},K={K},F={F},T={T})')
     return out
-
-
-PA_METRIC = {'cos': 0, 'multiply': 1, 'euclidean': 2}
 
 
 def _strides3(x):
     """element strides of (utterance, class, bin) of a (U,K,F,T) tensor with contiguous frames"""
     assert x.stride(-1) == 1 or x.shape[-1] == 1, x.stride()
     return (ctypes.c_int64 * 3)(x.stride(0), x.stride(1), x.stride(2))
-
-
-def _view_ptr(x):
-    """device pointer of a (possibly strided) view; the strides travel separately"""
-    assert x.is_cuda, x.device
-    return ctypes.c_void_p(x.data_ptr())
 
 
 def pa_pairwise_mapping(mask, reference, metric, optimal, *, mapping=None, col0=0,
@@ -525,22 +478,18 @@ def pa_pairwise_mapping(mask, reference, metric, optimal, *, mapping=None, col0=
         mapping = t.empty((U, K, col0 + F), dtype=t.int32, device=mask.device)
     scores = t.empty((U, F, K, K), dtype=t.float64, device=mask.device) if want_scores else None
     st = t.zeros((U,), dtype=t.int32, device=mask.device)
-    rc = _lib.load().pbbss_pa_pairwise_mapping(
-        _lib.handle(mask.device.index), _view_ptr(mask), _view_ptr(reference), U, K, F, T,
-        _strides3(mask), _strides3(reference), PA_METRIC[metric], int(bool(optimal)),
-        _lib.ptr(scores) if want_scores else None, _lib.ptr(mapping), int(mapping.shape[-1]),
-        int(col0), _lib.ptr(st), _lib.stream_ptr(mask.device.index))
-    _lib.check(rc, f'pa_pairwise_mapping(U={U},K={K},F={F},T={T},{metric})')
+    _lib.launch('pbbss_pa_pairwise_mapping', mask.device, _lib.view_ptr(mask),
+                _lib.view_ptr(reference), U, K, F, T, _strides3(mask), _strides3(reference),
+                PA_METRIC[metric], bool(optimal), scores, mapping, mapping.shape[-1], col0, st,
+                what=f'pa_pairwise_mapping(U={U},K={K},F={F},T={T},{metric})')
     return mapping, scores, st
 
 
 def pa_compose_mapping(mapping):
     """pbbss_pa_compose_mapping, in place on mapping int32 (U,K,F)."""
     U, K, F = mapping.shape
-    rc = _lib.load().pbbss_pa_compose_mapping(
-        _lib.handle(mapping.device.index), _lib.ptr(mapping), U, K, F,
-        _lib.stream_ptr(mapping.device.index))
-    _lib.check(rc, f'pa_compose_mapping(U={U},K={K},F={F})')
+    _lib.launch('pbbss_pa_compose_mapping', mapping.device, mapping, U, K, F,
+                what=f'pa_compose_mapping(U={U},K={K},F={F})')
     return mapping
 
 
@@ -550,10 +499,8 @@ def pa_mapping_from_scores(scores, optimal):
     N, K, _ = scores.shape
     mapping = t.empty((K, N), dtype=t.int32, device=scores.device)
     st = t.zeros((1,), dtype=t.int32, device=scores.device)
-    rc = _lib.load().pbbss_pa_mapping_from_scores(
-        _lib.handle(scores.device.index), _lib.ptr(scores), N, K, int(bool(optimal)),
-        _lib.ptr(mapping), _lib.ptr(st), _lib.stream_ptr(scores.device.index))
-    _lib.check(rc, f'pa_mapping_from_scores(N={N},K={K})')
+    _lib.launch('pbbss_pa_mapping_from_scores', scores.device, scores, N, K, bool(optimal),
+                mapping, st, what=f'pa_mapping_from_scores(N={N},K={K})')
     return mapping, st
 
 
@@ -597,16 +544,13 @@ def cwmm_fit(y, K, spline, *, gamma0=None, model=None, iterations=100, saliency=
         out_st = t.zeros((B, K), dtype=t.int32, device=dev)
         out_aff = t.empty((B, K, T), dtype=f64, device=dev) if final_predict else None
         out_lp = t.empty((B, K, T), dtype=f64, device=dev) if want_log_pdf else None
-        rc = _lib.load().pbbss_cwmm_fit(
-            _lib.handle(dev.index), _lib.ptr(y), B, T, D, K, _lib.ptr(gamma0), _lib.ptr(in_mode),
-            _lib.ptr(in_conc), _lib.ptr(in_w), _lib.ptr(saliency), ctypes.byref(opts),
-            None if spline is None else _lib.ptr(spline['t']),
-            None if spline is None else _lib.ptr(spline['c']),
-            _lib.ptr(out_mode), _lib.ptr(out_conc), _lib.ptr(out_w), _lib.ptr(out_st),
-            _lib.ptr(out_aff), _lib.ptr(out_lp), _lib.stream_ptr(dev.index))
-        if shared and rc == _lib.ERR_UNSUPPORTED:
+        rc = _lib.launch('pbbss_cwmm_fit', dev, y, B, T, D, K, gamma0, in_mode, in_conc, in_w,
+                         saliency, opts, None if spline is None else spline['t'],
+                         None if spline is None else spline['c'], out_mode, out_conc, out_w,
+                         out_st, out_aff, out_lp, what=f'cwmm_fit(B={B},T={T},D={D},K={K})',
+                         accept=_NOT_SERVED if shared else ())
+        if rc == _lib.ERR_UNSUPPORTED:
             return None
-        _lib.check(rc, f'cwmm_fit(B={B},T={T},D={D},K={K})')
         return dict(mode=out_mode, concentration=out_conc, weight=out_w, status=out_st,
                     affiliation=out_aff, log_pdf=out_lp)
 
@@ -653,12 +597,9 @@ def cbmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, we
     out_st = t.zeros((B, K), dtype=t.int32, device=dev)
     out_aff = t.empty((B, K, T), dtype=f64, device=dev) if final_predict else None
     out_lp = t.empty((B, K, T), dtype=f64, device=dev) if want_log_pdf else None
-    rc = _lib.load().pbbss_cbmm_fit(
-        _lib.handle(dev.index), _lib.ptr(y), B, T, D, K, _lib.ptr(gamma0), _lib.ptr(in_v),
-        _lib.ptr(in_l), _lib.ptr(in_w), _lib.ptr(saliency), ctypes.byref(opts), _lib.ptr(out_v),
-        _lib.ptr(out_l), _lib.ptr(out_c), _lib.ptr(out_w), _lib.ptr(out_st), _lib.ptr(out_aff),
-        _lib.ptr(out_lp), _lib.stream_ptr(dev.index))
-    _lib.check(rc, f'cbmm_fit(B={B},T={T},D={D},K={K})')
+    _lib.launch('pbbss_cbmm_fit', dev, y, B, T, D, K, gamma0, in_v, in_l, in_w, saliency, opts,
+                out_v, out_l, out_c, out_w, out_st, out_aff, out_lp,
+                what=f'cbmm_fit(B={B},T={T},D={D},K={K})')
     if check_status:
         _status_raise_em(out_st, 'CBMMTrainer.fit')
     return dict(eigvec=out_v, eigval=out_l, log_norm=out_c, weight=out_w, status=out_st,
@@ -673,10 +614,8 @@ def cbingham_find_eigenvalues(scatter, eigenvalue_eps=1e-8, max_concentration=fl
     N, D = scatter.shape
     lam = t.empty((N, D), dtype=t.float64, device=dev)
     st = t.zeros((N,), dtype=t.int32, device=dev)
-    rc = _lib.load().pbbss_cbingham_find_eigenvalues(
-        _lib.handle(dev.index), _lib.ptr(scatter), N, D, float(eigenvalue_eps),
-        float(max_concentration), _lib.ptr(lam), _lib.ptr(st), _lib.stream_ptr(dev.index))
-    _lib.check(rc, f'cbingham_find_eigenvalues(N={N},D={D})')
+    _lib.launch('pbbss_cbingham_find_eigenvalues', dev, scatter, N, D, eigenvalue_eps,
+                max_concentration, lam, st, what=f'cbingham_find_eigenvalues(N={N},D={D})')
     if check_status:
         _status_raise_em(st, 'ComplexBinghamTrainer.find_eigenvalues_v3')
     return lam, st
@@ -697,12 +636,9 @@ def deflation_seed(y, K, *, saliency=None, permutation_free=True, neighbors=5, e
     assert saliency is None or (saliency.shape == (B, F, T) and saliency.dtype == t.float64)
     assert state is None or (state.shape == (B, F, T) and state.dtype == t.float64)
     peak = t.empty((B, K - 1, F), dtype=t.int32, device=dev) if want_peak else None
-    rc = _lib.load().pbbss_deflation_seed(
-        _lib.handle(dev.index), _lib.ptr(y), int(y.dtype == t.complex128), B, F, T, D, int(K),
-        _lib.ptr(saliency), int(bool(permutation_free)), int(neighbors), float(eps), int(r0),
-        int(r1), int(bool(finalize)), _lib.ptr(state), _lib.ptr(out), _lib.ptr(peak),
-        _lib.stream_ptr(dev.index))
-    _lib.check(rc, f'deflation_seed(B={B},F={F},T={T},D={D},K={K})')
+    _lib.launch('pbbss_deflation_seed', dev, y, y.dtype == t.complex128, B, F, T, D, K, saliency,
+                bool(permutation_free), neighbors, eps, r0, r1, bool(finalize), state, out, peak,
+                what=f'deflation_seed(B={B},F={F},T={T},D={D},K={K})')
     return (out, peak) if want_peak else out
 
 
@@ -714,59 +650,75 @@ def wmwf(target, noise, distortion_weight=1.0, frequency_dependent=False):
     num = t.empty((N, D), dtype=t.complex128, device=target.device)
     den = t.empty((N, D), dtype=t.complex128, device=target.device)
     st = t.zeros((N,), dtype=t.int32, device=target.device)
-    rc = _lib.load().pbbss_wmwf(
-        _lib.handle(target.device.index), _lib.ptr(target), _lib.ptr(noise), N, D,
-        float(distortion_weight), int(bool(frequency_dependent)), _lib.ptr(mat),
-        _lib.ptr(num), _lib.ptr(den), _lib.ptr(st), _lib.stream_ptr(target.device.index))
-    _lib.check(rc, f'wmwf(N={N},D={D})')
+    _lib.launch('pbbss_wmwf', target.device, target, noise, N, D, distortion_weight,
+                bool(frequency_dependent), mat, num, den, st, what=f'wmwf(N={N},D={D})')
     return mat, num, den, st
 
 
-_DHTV_PROBE = {}  # (device index, host thread) -> last set_dhtv_probe flag word (default 0)
-_SPLIT_TAIL = {}  # (device index, host thread) -> last set_split_tail value (default: on)
-
-
-def set_split_tail(enable, device_index=None):
-    """pbbss_set_split_tail: toggle the split-bin handling of remainder problems."""
-    _lib.check(_lib.load().pbbss_set_split_tail(_lib.handle(device_index), int(bool(enable))),
-               'set_split_tail')
-    _SPLIT_TAIL[_handle_key(device_index)] = bool(enable)
-
-
-def split_tail(device_index=None):
-    """The split-tail setting in force on this thread's handle (handles are created with it on)."""
-    return _SPLIT_TAIL.get(_handle_key(device_index), True)
-
-
-def set_spin_limit(polls, device_index=None):
-    """pbbss_set_spin_limit (test knob): polls before a bounded inter-workgroup wait gives up;
-    0 = defaults.  A tiny value provokes real time-outs of the split / team protocols."""
-    _lib.check(_lib.load().pbbss_set_spin_limit(_lib.handle(device_index), int(polls)),
-               'set_spin_limit')
-
-
-def split_reset(device_index=None):
-    """pbbss_split_reset: consume a reported time-out (re-zero the protocol counters and the
-    sticky flag of split_error) after the device has drained."""
-    _lib.check(_lib.load().pbbss_split_reset(_lib.handle(device_index)), 'split_reset')
-
-
-_DHTV_TEAM = {}  # (device index, host thread) -- one C handle each -- -> last set_dhtv_team value
+# (device index, host thread) -- one C handle each -- -> {'split_tail' | 'dhtv_team' |
+# 'dhtv_probe': the value this layer last set}; a getter without an entry answers the default
+# the library creates the handle with
+_SETTINGS = {}
 
 
 def _handle_key(device_index):
-    import threading
     if device_index is None:
         device_index = _lib.require_gpu().cuda.current_device()
     return (device_index, threading.get_ident())
 
 
+def _settings(device_index):
+    return _SETTINGS.setdefault(_handle_key(device_index), {})
+
+
+def set_split_tail(enable, device_index=None):
+    """pbbss_set_split_tail: toggle the split-bin handling of remainder problems."""
+    _lib.control('pbbss_set_split_tail', device_index, bool(enable), what='set_split_tail')
+    _settings(device_index)['split_tail'] = bool(enable)
+
+
+def split_tail(device_index=None):
+    """The split-tail setting in force on this thread's handle (handles are created with it on)."""
+    return _settings(device_index).get('split_tail', True)
+
+
+def set_spin_limit(polls, device_index=None):
+    """pbbss_set_spin_limit (test knob): polls before a bounded inter-workgroup wait gives up;
+    0 = defaults.  A tiny value provokes real time-outs of the split / team protocols."""
+    _lib.control('pbbss_set_spin_limit', device_index, polls, what='set_spin_limit')
+
+
+def split_reset(device_index=None):
+    """pbbss_split_reset: consume a reported time-out (re-zero the protocol counters and the
+    sticky flag of split_error) after the device has drained."""
+    _lib.control('pbbss_split_reset', device_index, what='split_reset')
+
+
+def split_error(device_index=None):
+    """pbbss_split_error: 1 if an inter-workgroup wait of a split launch ever timed out."""
+    flag = ctypes.c_int()
+    _lib.control('pbbss_split_error', device_index, flag, what='split_error')
+    return int(flag.value)
+
+
 def set_dhtv_team(workgroups_per_utterance, device_index=None):
     """pbbss_set_dhtv_team: 0 automatic, 1 one workgroup per utterance, >= 2 frame-slice kernel,
     -2..-32 bin-chunk team kernel of that size."""
-    _lib.check(_lib.load().pbbss_set_dhtv_team(_lib.handle(device_index),
-                                               int(workgroups_per_utterance)), 'set_dhtv_team')
-    _DHTV_TEAM[_handle_key(device_index)] = int(workgroups_per_utterance)
+    _lib.control('pbbss_set_dhtv_team', device_index, workgroups_per_utterance,
+                 what='set_dhtv_team')
+    _settings(device_index)['dhtv_team'] = int(workgroups_per_utterance)
+
+
+def dhtv_team(device_index=None):
+    """The team setting in force on this thread's handle: its last set_dhtv_team, else
+    PBBSS_DHTV_TEAM (read by the library when the handle is created), else 0 = automatic."""
+    settings = _settings(device_index)
+    if 'dhtv_team' in settings:
+        return settings['dhtv_team']
+    try:
+        return int(os.environ.get('PBBSS_DHTV_TEAM', '0'))
+    except ValueError:
+        return 0
 
 
 def set_dhtv_probe(enable, device_index=None):
@@ -775,34 +727,13 @@ def set_dhtv_probe(enable, device_index=None):
     every EM iteration).  `enable` True / False, or the flag word of the C call (2: the aligned
     features are not written, 3: probe + no features)."""
     flags = int(enable) if isinstance(enable, int) and not isinstance(enable, bool) else int(bool(enable))
-    _lib.check(_lib.load().pbbss_set_dhtv_probe(_lib.handle(device_index), flags),
-               'set_dhtv_probe')
-    _DHTV_PROBE[_handle_key(device_index)] = flags
+    _lib.control('pbbss_set_dhtv_probe', device_index, flags, what='set_dhtv_probe')
+    _settings(device_index)['dhtv_probe'] = flags
 
 
 def dhtv_probe(device_index=None):
     """The probe flag word in force on this thread's handle (its last set_dhtv_probe, else 0)."""
-    return _DHTV_PROBE.get(_handle_key(device_index), 0)
-
-
-def dhtv_team(device_index=None):
-    """The team setting in force on this thread's handle: its last set_dhtv_team, else
-    PBBSS_DHTV_TEAM (read by the library when the handle is created), else 0 = automatic."""
-    key = _handle_key(device_index)
-    if key in _DHTV_TEAM:
-        return _DHTV_TEAM[key]
-    try:
-        return int(os.environ.get('PBBSS_DHTV_TEAM', '0'))
-    except ValueError:
-        return 0
-
-
-def split_error(device_index=None):
-    """pbbss_split_error: 1 if an inter-workgroup wait of a split launch ever timed out."""
-    flag = ctypes.c_int()
-    _lib.check(_lib.load().pbbss_split_error(_lib.handle(device_index), ctypes.byref(flag)),
-               'split_error')
-    return int(flag.value)
+    return _settings(device_index).get('dhtv_probe', 0)
 
 
 # ---- N2/N3: real-embedding mixtures and joint spatial+spectral models ---------
@@ -833,10 +764,10 @@ def embed_log_pdf(y, kind, mean, scale):
     B, N, E = y.shape
     K = mean.shape[1]
     out = t.empty((B, K, N), dtype=t.float64, device=y.device)
-    rc = _lib.load().pbbss_embed_log_pdf(
-        _lib.handle(y.device.index), _lib.ptr(y), int(y.dtype == t.float64), B, N, E, K, int(kind),
-        _lib.ptr(mean), _lib.ptr(scale), _lib.ptr(out), _lib.stream_ptr(y.device.index))
-    _embed_check(rc, f'embed_log_pdf(B={B},N={N},E={E},K={K})', K)
+    what = f'embed_log_pdf(B={B},N={N},E={E},K={K})'
+    rc = _lib.launch('pbbss_embed_log_pdf', y.device, y, y.dtype == t.float64, B, N, E, K, kind,
+                     mean, scale, out, what=what, accept=_NOT_SERVED)
+    _embed_check(rc, what, K)
     return out
 
 
@@ -852,11 +783,11 @@ def embed_fit(y, kind, weights, *, normalize=False, min_concentration=1e-10,
     mean = t.empty((B, K, E), dtype=t.float64, device=y.device)
     scale = t.empty((B, K, E) if kind == _lib.EMBED_GAUSS_DIAG else (B, K), dtype=t.float64,
                     device=y.device)
-    rc = _lib.load().pbbss_embed_fit(
-        _lib.handle(y.device.index), _lib.ptr(y), int(y.dtype == t.float64), B, N, E, K, int(kind),
-        int(bool(normalize)), _lib.ptr(weights), float(min_concentration),
-        float(max_concentration), _lib.ptr(mean), _lib.ptr(scale), _lib.stream_ptr(y.device.index))
-    _embed_check(rc, f'embed_fit(B={B},N={N},E={E},K={K})', K)
+    what = f'embed_fit(B={B},N={N},E={E},K={K})'
+    rc = _lib.launch('pbbss_embed_fit', y.device, y, y.dtype == t.float64, B, N, E, K, kind,
+                     bool(normalize), weights, min_concentration, max_concentration, mean, scale,
+                     what=what, accept=_NOT_SERVED)
+    _embed_check(rc, what, K)
     return mean, scale
 
 
@@ -886,12 +817,10 @@ def vmfmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, w
         assert in_mean.shape == (B, K, E) and in_conc.shape == (B, K) and in_w.shape == (B, K)
     else:
         assert gamma0.shape == (B, K, N) and gamma0.dtype == f64
-    rc = _lib.load().pbbss_vmfmm_fit(
-        _lib.handle(dev.index), _lib.ptr(y), B, N, E, K, _lib.ptr(gamma0), _lib.ptr(in_mean),
-        _lib.ptr(in_conc), _lib.ptr(in_w), _lib.ptr(saliency), ctypes.byref(opts),
-        _lib.ptr(mean), _lib.ptr(conc), _lib.ptr(weight), _lib.ptr(aff), _lib.ptr(lp),
-        _lib.stream_ptr(dev.index))
-    _embed_check(rc, f'vmfmm_fit(B={B},N={N},E={E},K={K})', K)
+    what = f'vmfmm_fit(B={B},N={N},E={E},K={K})'
+    rc = _lib.launch('pbbss_vmfmm_fit', dev, y, B, N, E, K, gamma0, in_mean, in_conc, in_w,
+                     saliency, opts, mean, conc, weight, aff, lp, what=what, accept=_NOT_SERVED)
+    _embed_check(rc, what, K)
     return dict(mean=mean, concentration=conc, weight=weight, affiliation=aff, log_pdf=lp)
 
 
@@ -904,10 +833,8 @@ def gauss_full_fit(y, weights):
     assert weights.shape == (B, K, N) and weights.dtype == t.float64, (weights.shape, y.shape)
     mean = t.empty((B, K, E), dtype=t.float64, device=y.device)
     cov = t.empty((B, K, E, E), dtype=t.float64, device=y.device)
-    rc = _lib.load().pbbss_gauss_full_fit(
-        _lib.handle(y.device.index), _lib.ptr(y), int(y.dtype == t.float64), B, N, E, K,
-        _lib.ptr(weights), _lib.ptr(mean), _lib.ptr(cov), _lib.stream_ptr(y.device.index))
-    _lib.check(rc, f'gauss_full_fit(B={B},N={N},E={E},K={K})')
+    _lib.launch('pbbss_gauss_full_fit', y.device, y, y.dtype == t.float64, B, N, E, K, weights,
+                mean, cov, what=f'gauss_full_fit(B={B},N={N},E={E},K={K})')
     return mean, cov
 
 
@@ -920,11 +847,8 @@ def gauss_full_log_pdf(y, mean, cov):
     assert mean.shape == (B, K, E) and cov.shape == (B, K, E, E), (mean.shape, cov.shape)
     out = t.empty((B, K, N), dtype=t.float64, device=y.device)
     st = t.zeros((1,), dtype=t.int32, device=y.device)
-    rc = _lib.load().pbbss_gauss_full_log_pdf(
-        _lib.handle(y.device.index), _lib.ptr(y), int(y.dtype == t.float64), B, N, E, K,
-        _lib.ptr(mean), _lib.ptr(cov), _lib.ptr(out), _lib.ptr(st),
-        _lib.stream_ptr(y.device.index))
-    _lib.check(rc, f'gauss_full_log_pdf(B={B},N={N},E={E},K={K})')
+    _lib.launch('pbbss_gauss_full_log_pdf', y.device, y, y.dtype == t.float64, B, N, E, K, mean,
+                cov, out, st, what=f'gauss_full_log_pdf(B={B},N={N},E={E},K={K})')
     return out, st
 
 
@@ -954,12 +878,11 @@ def gmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, wei
         assert gamma0.shape == (B, K, N) and gamma0.dtype == f64
     if fixed_covariance is not None:
         assert fixed_covariance.shape == (B, K) and fixed_covariance.dtype == f64
-    rc = _lib.load().pbbss_gmm_fit(
-        _lib.handle(dev.index), _lib.ptr(y), B, N, E, K, _lib.ptr(gamma0), _lib.ptr(in_mean),
-        _lib.ptr(in_cov), _lib.ptr(in_w), _lib.ptr(saliency), _lib.ptr(fixed_covariance),
-        ctypes.byref(opts), _lib.ptr(mean), _lib.ptr(cov), _lib.ptr(weight), _lib.ptr(aff),
-        _lib.ptr(lp), _lib.stream_ptr(dev.index))
-    _embed_check(rc, f'gmm_fit(B={B},N={N},E={E},K={K})', K)
+    what = f'gmm_fit(B={B},N={N},E={E},K={K})'
+    rc = _lib.launch('pbbss_gmm_fit', dev, y, B, N, E, K, gamma0, in_mean, in_cov, in_w, saliency,
+                     fixed_covariance, opts, mean, cov, weight, aff, lp, what=what,
+                     accept=_NOT_SERVED)
+    _embed_check(rc, what, K)
     return dict(mean=mean, covariance=cov, weight=weight, affiliation=aff, log_pdf=lp)
 
 
@@ -989,12 +912,9 @@ def gmm_full_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None
         assert gamma0.shape == (B, K, N) and gamma0.dtype == f64
     if fixed_covariance is not None:
         assert fixed_covariance.shape == (B, K, E, E) and fixed_covariance.dtype == f64
-    rc = _lib.load().pbbss_gmm_full_fit(
-        _lib.handle(dev.index), _lib.ptr(y), B, N, E, K, _lib.ptr(gamma0), _lib.ptr(in_mean),
-        _lib.ptr(in_cov), _lib.ptr(in_w), _lib.ptr(saliency), _lib.ptr(fixed_covariance),
-        ctypes.byref(opts), _lib.ptr(mean), _lib.ptr(cov), _lib.ptr(weight), _lib.ptr(aff),
-        _lib.ptr(lp), _lib.ptr(st), _lib.stream_ptr(dev.index))
-    _lib.check(rc, f'gmm_full_fit(B={B},N={N},E={E},K={K})')
+    _lib.launch('pbbss_gmm_full_fit', dev, y, B, N, E, K, gamma0, in_mean, in_cov, in_w, saliency,
+                fixed_covariance, opts, mean, cov, weight, aff, lp, st,
+                what=f'gmm_full_fit(B={B},N={N},E={E},K={K})')
     return dict(mean=mean, covariance=cov, weight=weight, affiliation=aff, log_pdf=lp, status=st)
 
 
@@ -1006,14 +926,11 @@ def estimate_mixture_weight(affiliation, saliency, reduce_inner, reduce_n):
     Bo, Bi, K, N = affiliation.shape
     out = t.empty((Bo, 1 if reduce_inner else Bi, K, 1 if reduce_n else N), dtype=t.float64,
                   device=affiliation.device)
-    rc = _lib.load().pbbss_estimate_mixture_weight(
-        _lib.handle(affiliation.device.index), _lib.ptr(affiliation), _lib.ptr(saliency), Bo, Bi, K,
-        N, int(bool(reduce_inner)), int(bool(reduce_n)), _lib.ptr(out),
-        _lib.stream_ptr(affiliation.device.index))
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, f'estimate_mixture_weight(Bo={Bo},Bi={Bi},K={K},N={N})')
-    return out
+    rc = _lib.launch('pbbss_estimate_mixture_weight', affiliation.device, affiliation, saliency,
+                     Bo, Bi, K, N, bool(reduce_inner), bool(reduce_n), out,
+                     what=f'estimate_mixture_weight(Bo={Bo},Bi={Bi},K={K},N={N})',
+                     accept=_NOT_SERVED)
+    return None if rc == _lib.ERR_UNSUPPORTED else out
 
 
 def log_pdf_to_affiliation(log_pdf, weight, activity=None, affiliation_eps=0.):
@@ -1025,11 +942,9 @@ def log_pdf_to_affiliation(log_pdf, weight, activity=None, affiliation_eps=0.):
     out = t.empty((B, K, N), dtype=t.float64, device=log_pdf.device)
     if activity is not None:
         assert activity.shape == (B, K, N) and activity.dtype == t.uint8
-    rc = _lib.load().pbbss_log_pdf_to_affiliation(
-        _lib.handle(log_pdf.device.index), _lib.ptr(log_pdf.contiguous()), B, K, N, _lib.ptr(w),
-        st[0], st[1], st[2], _lib.ptr(activity), float(affiliation_eps), _lib.ptr(out),
-        _lib.stream_ptr(log_pdf.device.index))
-    _lib.check(rc, f'log_pdf_to_affiliation(B={B},K={K},N={N})')
+    _lib.launch('pbbss_log_pdf_to_affiliation', log_pdf.device, log_pdf.contiguous(), B, K, N, w,
+                st[0], st[1], st[2], activity, affiliation_eps, out,
+                what=f'log_pdf_to_affiliation(B={B},K={K},N={N})')
     return out
 
 
@@ -1060,12 +975,11 @@ def log_pdf_to_affiliation_inline_pa(spatial_log_pdf, spectral_log_pdf, weight, 
     perm = t.empty((F, K), dtype=t.int32, device=dev) if want_permutation else None
     if activity is not None:
         assert activity.shape == (F, K, T) and activity.dtype == t.uint8
-    rc = _lib.load().pbbss_log_pdf_to_affiliation_inline_pa(
-        _lib.handle(dev.index), _lib.ptr(spatial_log_pdf.to(t.float64).contiguous()),
-        _lib.ptr(spectral_log_pdf.to(t.float64).contiguous()), F, K, T, _lib.ptr(w), st[0], st[1],
-        st[2], _lib.ptr(activity), float(affiliation_eps), _lib.ptr(out), _lib.ptr(perm),
-        _lib.stream_ptr(dev.index))
-    _lib.check(rc, f'log_pdf_to_affiliation_inline_pa(F={F},K={K},T={T})')
+    _lib.launch('pbbss_log_pdf_to_affiliation_inline_pa', dev,
+                spatial_log_pdf.to(t.float64).contiguous(),
+                spectral_log_pdf.to(t.float64).contiguous(), F, K, T, w, st[0], st[1], st[2],
+                activity, affiliation_eps, out, perm,
+                what=f'log_pdf_to_affiliation_inline_pa(F={F},K={K},T={T})')
     return (out, perm) if want_permutation else out
 
 
@@ -1119,19 +1033,17 @@ def joint_fit(observation, embedding, K, kind, *, gamma0=None, model=None, itera
         assert tuple(in_scale.shape) == scale_shape, (tuple(in_scale.shape), scale_shape)
     else:
         assert gamma0.shape == (F, K, T) and gamma0.dtype == f64
-    rc = _lib.load().pbbss_joint_fit(
-        _lib.handle(dev.index), _lib.ptr(observation), _lib.ptr(embedding), F, T, D, E, K,
-        _lib.ptr(gamma0), _lib.ptr(in_vec), _lib.ptr(in_val), _lib.ptr(in_w), _lib.ptr(in_mean),
-        _lib.ptr(in_scale), _lib.ptr(saliency), ctypes.byref(opts), _lib.ptr(eigvec),
-        _lib.ptr(eigval), _lib.ptr(weight), _lib.ptr(mean), _lib.ptr(scale), _lib.ptr(status),
-        _lib.ptr(aff), _lib.stream_ptr(dev.index))
+    what = f'joint_fit(F={F},T={T},D={D},E={E},K={K})'
+    rc = _lib.launch('pbbss_joint_fit', dev, observation, embedding, F, T, D, E, K, gamma0, in_vec,
+                     in_val, in_w, in_mean, in_scale, saliency, opts, eigvec, eigval, weight, mean,
+                     scale, status, aff, what=what, accept=_NOT_SERVED)
     if rc == _lib.ERR_UNSUPPORTED and (K > JOINT_MAX_CLASSES or (inline_pa and K > 6)
                                        or (sharded and K > 8)):
         raise NotImplementedError(
-            f'joint_fit(F={F},T={T},D={D},E={E},K={K}): the joint models serve 1 <= K <= '
+            f'{what}: the joint models serve 1 <= K <= '
             f'{JOINT_MAX_CLASSES} classes (the generic-size spatial kernels), inline permutation '
             'alignment 1 <= K <= 6, bin-sharded fits 1 <= K <= 8')
-    _lib.check(rc, f'joint_fit(F={F},T={T},D={D},E={E},K={K})')
+    _lib.check(rc, what)
     if kind == _lib.EMBED_GAUSS_FULL and int(status[0, 0].item()) & _lib.ST_NOT_POSDEF:
         raise ValueError(  # sklearn's _compute_precision_cholesky via gaussian.py:26
             'Fitting the mixture model failed because some components have ill-defined empirical '
@@ -1149,10 +1061,8 @@ def lcmv(atf, response, noise):
     K, F, D = atf.shape
     w = t.empty((F, D), dtype=t.complex128, device=atf.device)
     st = t.zeros((F,), dtype=t.int32, device=atf.device)
-    rc = _lib.load().pbbss_lcmv(_lib.handle(atf.device.index), _lib.ptr(atf), _lib.ptr(response),
-                                _lib.ptr(noise), F, D, K, _lib.ptr(w), _lib.ptr(st),
-                                _lib.stream_ptr(atf.device.index))
-    _lib.check(rc, f'lcmv(K={K},F={F},D={D})')
+    _lib.launch('pbbss_lcmv', atf.device, atf, response, noise, F, D, K, w, st,
+                what=f'lcmv(K={K},F={F},D={D})')
     return w, st
 
 
@@ -1165,10 +1075,8 @@ def phase_correction(vector):
     rest = 1 if two_d else int(np.prod(vector.shape[1:-2], dtype=np.int64))
     out = t.empty_like(vector)
     scratch = t.empty((max(lead * rest * (F - 1), 1),), dtype=t.complex128, device=vector.device)
-    rc = _lib.load().pbbss_phase_correction(
-        _lib.handle(vector.device.index), _lib.ptr(vector), lead, rest, F, D, int(two_d),
-        _lib.ptr(scratch), _lib.ptr(out), _lib.stream_ptr(vector.device.index))
-    _lib.check(rc, f'phase_correction(shape={tuple(vector.shape)})')
+    _lib.launch('pbbss_phase_correction', vector.device, vector, lead, rest, F, D, two_d, scratch,
+                out, what=f'phase_correction(shape={tuple(vector.shape)})')
     return out
 
 
@@ -1176,10 +1084,8 @@ def snr_postfilter(w, target, noise):
     t = _t()
     F, D = w.shape
     out = t.empty((F,), dtype=t.complex128, device=w.device)
-    rc = _lib.load().pbbss_snr_postfilter(_lib.handle(w.device.index), _lib.ptr(w),
-                                          _lib.ptr(target), _lib.ptr(noise), F, D, _lib.ptr(out),
-                                          _lib.stream_ptr(w.device.index))
-    _lib.check(rc, f'snr_postfilter(F={F},D={D})')
+    _lib.launch('pbbss_snr_postfilter', w.device, w, target, noise, F, D, out,
+                what=f'snr_postfilter(F={F},D={D})')
     return out
 
 
@@ -1189,10 +1095,8 @@ def reference_channel_terms(w_mat, target, noise):
     F, D, _ = w_mat.shape
     num = t.empty((F, D), dtype=t.complex128, device=w_mat.device)
     den = t.empty((F, D), dtype=t.complex128, device=w_mat.device)
-    rc = _lib.load().pbbss_reference_channel_terms(
-        _lib.handle(w_mat.device.index), _lib.ptr(w_mat), _lib.ptr(target), _lib.ptr(noise), F, D,
-        _lib.ptr(num), _lib.ptr(den), _lib.stream_ptr(w_mat.device.index))
-    _lib.check(rc, f'reference_channel_terms(F={F},D={D})')
+    _lib.launch('pbbss_reference_channel_terms', w_mat.device, w_mat, target, noise, F, D, num,
+                den, what=f'reference_channel_terms(F={F},D={D})')
     return num, den
 
 
@@ -1201,10 +1105,8 @@ def rank_one_approximation(covariance, vector):
     t = _t()
     N, D = vector.shape
     out = t.empty((N, D, D), dtype=t.complex128, device=vector.device)
-    rc = _lib.load().pbbss_rank_one_approximation(
-        _lib.handle(vector.device.index), _lib.ptr(covariance), _lib.ptr(vector), N, D,
-        _lib.ptr(out), _lib.stream_ptr(vector.device.index))
-    _lib.check(rc, f'rank_one_approximation(N={N},D={D})')
+    _lib.launch('pbbss_rank_one_approximation', vector.device, covariance, vector, N, D, out,
+                what=f'rank_one_approximation(N={N},D={D})')
     return out
 
 
@@ -1213,10 +1115,8 @@ def matvec(matrix, vector):
     t = _t()
     N, D = vector.shape
     out = t.empty((N, D), dtype=t.complex128, device=vector.device)
-    rc = _lib.load().pbbss_matvec(_lib.handle(vector.device.index), _lib.ptr(matrix),
-                                  _lib.ptr(vector), N, D, _lib.ptr(out),
-                                  _lib.stream_ptr(vector.device.index))
-    _lib.check(rc, f'matvec(N={N},D={D})')
+    _lib.launch('pbbss_matvec', vector.device, matrix, vector, N, D, out,
+                what=f'matvec(N={N},D={D})')
     return out
 
 
@@ -1224,10 +1124,8 @@ def distortionless_normalization(w, atf, noise):
     t = _t()
     F, D = w.shape
     out = t.empty((F, D), dtype=t.complex128, device=w.device)
-    rc = _lib.load().pbbss_distortionless_normalization(
-        _lib.handle(w.device.index), _lib.ptr(w), _lib.ptr(atf), _lib.ptr(noise), F, D,
-        _lib.ptr(out), _lib.stream_ptr(w.device.index))
-    _lib.check(rc, f'distortionless_normalization(F={F},D={D})')
+    _lib.launch('pbbss_distortionless_normalization', w.device, w, atf, noise, F, D, out,
+                what=f'distortionless_normalization(F={F},D={D})')
     return out
 
 
@@ -1235,10 +1133,8 @@ def zero_degree_normalization(vector, reference_channel):
     t = _t()
     N, D = vector.shape
     out = t.empty_like(vector)
-    rc = _lib.load().pbbss_zero_degree_normalization(
-        _lib.handle(vector.device.index), _lib.ptr(vector), N, D, int(reference_channel) % D,
-        _lib.ptr(out), _lib.stream_ptr(vector.device.index))
-    _lib.check(rc, f'zero_degree_normalization(N={N},D={D})')
+    _lib.launch('pbbss_zero_degree_normalization', vector.device, vector, N, D,
+                int(reference_channel) % D, out, what=f'zero_degree_normalization(N={N},D={D})')
     return out
 
 
@@ -1246,10 +1142,8 @@ def condition_covariance(x, gamma):
     t = _t()
     N, D, _ = x.shape
     out = t.empty_like(x)
-    rc = _lib.load().pbbss_condition_covariance(_lib.handle(x.device.index), _lib.ptr(x), N, D,
-                                                float(gamma), _lib.ptr(out),
-                                                _lib.stream_ptr(x.device.index))
-    _lib.check(rc, f'condition_covariance(N={N},D={D})')
+    _lib.launch('pbbss_condition_covariance', x.device, x, N, D, gamma, out,
+                what=f'condition_covariance(N={N},D={D})')
     return out
 
 
@@ -1258,10 +1152,8 @@ def apply_online_bf(vector, mix):
     t = _t()
     T, F, D = vector.shape
     out = t.empty((F, T), dtype=t.complex128, device=mix.device)
-    rc = _lib.load().pbbss_apply_online_beamforming_vector(
-        _lib.handle(mix.device.index), _lib.ptr(vector), _lib.ptr(mix),
-        int(mix.dtype == t.complex128), F, T, D, _lib.ptr(out), _lib.stream_ptr(mix.device.index))
-    _lib.check(rc, f'apply_online_bf(T={T},F={F},D={D})')
+    _lib.launch('pbbss_apply_online_beamforming_vector', mix.device, vector, mix,
+                mix.dtype == t.complex128, F, T, D, out, what=f'apply_online_bf(T={T},F={F},D={D})')
     return out
 
 
@@ -1287,11 +1179,9 @@ def stft(x, size, shift, window, *, fading=True, pad=True, layout=0, out_c128=Tr
     F = size // 2 + 1
     shape = (C, T, F) if layout == 0 else (F, T, C)
     out = t.empty(shape, dtype=t.complex128 if out_c128 else t.complex64, device=x.device)
-    rc = _lib.load().pbbss_stft(
-        _lib.handle(x.device.index), _lib.ptr(x), int(x.dtype == t.float64), C, N, int(size),
-        int(shift), wl, _lib.ptr(window), int(bool(fading)), int(bool(pad)), int(layout),
-        int(bool(out_c128)), _lib.ptr(out), _lib.stream_ptr(x.device.index))
-    _lib.check(rc, f'stft(C={C},N={N},size={size},shift={shift},window_length={wl})')
+    _lib.launch('pbbss_stft', x.device, x, x.dtype == t.float64, C, N, size, shift, wl, window,
+                bool(fading), bool(pad), layout, bool(out_c128), out,
+                what=f'stft(C={C},N={N},size={size},shift={shift},window_length={wl})')
     return out
 
 
@@ -1304,9 +1194,7 @@ def istft(X, size, shift, synthesis_window, *, fading=True):
     if n_out <= 0:
         raise ValueError(f'istft: {T} frames give no output samples')
     out = t.empty((C, n_out), dtype=t.float64, device=X.device)
-    rc = _lib.load().pbbss_istft(
-        _lib.handle(X.device.index), _lib.ptr(X), int(X.dtype == t.complex128), C, T, int(size),
-        int(shift), wl, _lib.ptr(synthesis_window), int(bool(fading)), _lib.ptr(out), n_out,
-        _lib.stream_ptr(X.device.index))
-    _lib.check(rc, f'istft(C={C},T={T},size={size},shift={shift},window_length={wl})')
+    _lib.launch('pbbss_istft', X.device, X, X.dtype == t.complex128, C, T, size, shift, wl,
+                synthesis_window, bool(fading), out, n_out,
+                what=f'istft(C={C},T={T},size={size},shift={shift},window_length={wl})')
     return out

@@ -15,8 +15,6 @@ periodic signals), that item's normal equations are fetched (`pbbss_bss_eval_sys
 with `numpy.linalg.lstsq` on the host and the energies are computed on the device from those
 filters (`pbbss_bss_eval_filters`) -- the same step `mir_eval` takes on a LinAlgError.
 """
-import ctypes
-
 import numpy as np
 
 from .. import _lib
@@ -47,11 +45,11 @@ def _batched(x, N):
 
 
 def _common(ref, est, filter_length):
+    """the arguments the three bss_eval exports share, behind the handle"""
     B, K, N = ref.shape
-    dev = ref.device.index
-    return (_lib.handle(dev), ctypes.c_void_p(ref.data_ptr()), ctypes.c_void_p(est.data_ptr()),
-            _signals.dtype_code(ref), B, K, est.shape[1], N, ref.stride(0) if B > 1 else 0,
-            ref.stride(1), est.stride(0), est.stride(1), filter_length)
+    return (_lib.view_ptr(ref), _lib.view_ptr(est), _signals.dtype_code(ref), B, K, est.shape[1],
+            N, ref.stride(0) if B > 1 else 0, ref.stride(1), est.stride(0), est.stride(1),
+            filter_length)
 
 
 def _outputs(t, B, K, device):
@@ -65,17 +63,14 @@ def _host_solve(ref, est, filter_length, compute_permutation):
     """the items of (ref, est) through the normal equations on the host: lstsq filters, then the
     energies on the device"""
     t = _lib.torch()
-    lib = _lib.load()
     B, K, N = ref.shape
     Ke, L = est.shape[1], filter_length
     n = K * L
-    dev = ref.device.index
     shared = B > 1 and ref.stride(0) == 0
     gram = t.empty((1 if shared else B, n, n), dtype=t.float64, device=ref.device)
     rhs = t.empty((B, Ke, n), dtype=t.float64, device=ref.device)
     common = _common(ref, est, L)
-    _lib.check(lib.pbbss_bss_eval_system(*common, _lib.ptr(gram), _lib.ptr(rhs),
-                                         _lib.stream_ptr(dev)), 'bss_eval_system')
+    _lib.launch('pbbss_bss_eval_system', ref.device, *common, gram, rhs, what='bss_eval_system')
     G, D = _lib.to_host(gram), _lib.to_host(rhs)
     blocks = [slice(j * L, (j + 1) * L) for j in range(K)]
 
@@ -97,29 +92,23 @@ def _host_solve(ref, est, filter_length, compute_permutation):
     values, selection, status = _outputs(t, B, K, ref.device)
     fa = t.from_numpy(f_all).to(ref.device)
     fs = t.from_numpy(f_single).to(ref.device)
-    _lib.check(lib.pbbss_bss_eval_filters(
-        *common, int(compute_permutation), _lib.ptr(fa), _lib.ptr(fs), _lib.ptr(values[0]),
-        _lib.ptr(values[1]), _lib.ptr(values[2]), _lib.ptr(selection), None, _lib.ptr(status),
-        _lib.stream_ptr(dev)), 'bss_eval_filters')
+    _lib.launch('pbbss_bss_eval_filters', ref.device, *common, compute_permutation, fa, fs,
+                values[0], values[1], values[2], selection, None, status, what='bss_eval_filters')
     return values, selection
 
 
 def _device_call(ref, est, filter_length, compute_permutation, info=None):
     """ref (B, K, N), est (B, Ke, N) views on one device -> values (3, B, K), selection (B, K)"""
     t = _lib.torch()
-    lib = _lib.load()
     B, K, N = ref.shape
     Ke = est.shape[1]
-    dev = ref.device.index
     values, selection, status = _outputs(t, B, K, ref.device)
     tables = t.empty((B, 3, Ke, K), dtype=t.float64, device=ref.device) if info is not None \
         else None
-    rc = lib.pbbss_bss_eval(
-        *_common(ref, est, filter_length), int(compute_permutation), _lib.ptr(values[0]),
-        _lib.ptr(values[1]), _lib.ptr(values[2]), _lib.ptr(selection), _lib.ptr(tables),
-        _lib.ptr(status), _lib.stream_ptr(dev))
-    _lib.check(rc, f'mir_eval_sources(B={B}, K={K}, Ke={Ke}, N={N}, '
-                   f'filter_length={filter_length})')
+    _lib.launch('pbbss_bss_eval', ref.device, *_common(ref, est, filter_length),
+                compute_permutation, values[0], values[1], values[2], selection, tables, status,
+                what=f'mir_eval_sources(B={B}, K={K}, Ke={Ke}, N={N}, '
+                     f'filter_length={filter_length})')
     st = _lib.to_host(status)
     if info is not None:
         info['status'] = st

@@ -6,8 +6,6 @@ reference asserts) gives NumPy out; a device tensor (float32 or float64, widened
 gives a float64 tensor on the same device, enqueued on the current stream without a host
 synchronisation.
 """
-import ctypes
-
 import numpy as np
 
 from .. import _lib
@@ -19,11 +17,9 @@ _MAX_ROWS = 8  # rows of each argument a lane keeps in registers (csrc/eval.hpp:
 
 def _launch(ref, est, B, Kr, Ke, N, strides, out):
     t = _lib.torch()
-    dev = ref.device.index
-    rc = _lib.load().pbbss_si_sdr(
-        _lib.handle(dev), ctypes.c_void_p(ref.data_ptr()), ctypes.c_void_p(est.data_ptr()),
-        int(ref.dtype == t.float64), B, Kr, Ke, N, *strides, _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(rc, f'si_sdr(B={B}, Kr={Kr}, Ke={Ke}, N={N})')
+    _lib.launch('pbbss_si_sdr', ref.device, _lib.view_ptr(ref), _lib.view_ptr(est),
+                ref.dtype == t.float64, B, Kr, Ke, N, *strides, out,
+                what=f'si_sdr(B={B}, Kr={Kr}, Ke={Ke}, N={N})')
 
 
 def _unit_last_axis(x, N):

@@ -51,11 +51,8 @@ def vad_rows(x, sample_rate):
     rows, N = x.shape
     out = t.empty((rows, N), dtype=t.float64, device=x.device)
     lengths = t.empty((rows,), dtype=t.int32, device=x.device)
-    dev = x.device.index
-    rc = _lib.load().pbbss_srmr_vad(
-        _lib.handle(dev), _lib.ptr(x), int(x.dtype == t.float64), rows, N, sample_rate,
-        _lib.ptr(out), _lib.ptr(lengths), _lib.stream_ptr(dev))
-    _lib.check(rc, f'srmr vad (rows={rows}, N={N}, sample_rate={sample_rate})')
+    _lib.launch('pbbss_srmr_vad', x.device, x, x.dtype == t.float64, rows, N, sample_rate, out,
+                lengths, what=f'srmr vad (rows={rows}, N={N}, sample_rate={sample_rate})')
     return out, lengths
 
 
@@ -91,9 +88,7 @@ def _srmr_rows(x, sample_rate, n, low_freq):
     """x: contiguous (rows, N) device tensor -> (rows,) float64 device tensor"""
     t = _lib.torch()
     rows, N = x.shape
-    dev = x.device.index
-    lib, handle, stream = _lib.load(), _lib.handle(dev), _lib.stream_ptr(dev)
-    cfs = gammatone.calculate_cfs(low_freq, sample_rate / 2, n)
+    cfs =gammatone.calculate_cfs(low_freq, sample_rate / 2, n)
     # one upload: gammatone stages, modulation filters, ERBs, cutoffs
     host = np.concatenate([
         gammatone.biquad_coefficients(cfs, sample_rate).ravel(),
@@ -108,13 +103,11 @@ def _srmr_rows(x, sample_rate, n, low_freq):
     bands = gammatone.filterbank_rows(y, lengths, gamma_coef)
     analytic = analytic_rows(bands, lengths.cpu().tolist()).contiguous()
     means = t.empty((rows, n, 8), dtype=t.float64, device=x.device)
-    rc = lib.pbbss_srmr_energies(handle, _lib.ptr(analytic), rows, N, _lib.ptr(lengths), n,
-                                 sample_rate, _lib.ptr(mod_coef), _lib.ptr(means), stream)
-    _lib.check(rc, f'srmr energies (rows={rows}, N={N}, n={n})')
+    _lib.launch('pbbss_srmr_energies', x.device, analytic, rows, N, lengths, n, sample_rate,
+                mod_coef, means, what=f'srmr energies (rows={rows}, N={N}, n={n})')
     out = t.empty((rows,), dtype=t.float64, device=x.device)
-    rc = lib.pbbss_srmr_score(handle, _lib.ptr(means), rows, n, _lib.ptr(erbs), _lib.ptr(cutoffs),
-                              _lib.ptr(out), stream)
-    _lib.check(rc, f'srmr score (rows={rows}, n={n})')
+    _lib.launch('pbbss_srmr_score', x.device, means, rows, n, erbs, cutoffs, out,
+                what=f'srmr score (rows={rows}, n={n})')
     return out
 
 

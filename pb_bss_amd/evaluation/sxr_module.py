@@ -11,7 +11,6 @@ a host synchronisation.  Beyond the reference, `input_sxr` and `output_sxr` take
 axes, and `output_sxr` can return the selection it found.
 """
 import collections
-import ctypes
 import operator
 
 import numpy as np
@@ -54,11 +53,9 @@ def _power(x, axis, keepdims):
     out = t.empty((rows,), dtype=t.float64, device=x.device)
     if rows:
         xc = x.permute(kept + reduced).contiguous()  # the rows in front; a copy only if needed
-        dev = x.device.index
-        rc = _lib.load().pbbss_signal_power(
-            _lib.handle(dev), ctypes.c_void_p(xc.data_ptr()), _signals.dtype_code(xc), rows,
-            length, length, _lib.ptr(out), _lib.stream_ptr(dev))
-        _lib.check(rc, f'signal_power(shape={tuple(x.shape)}, axis={axis})')
+        _lib.launch('pbbss_signal_power', x.device, _lib.view_ptr(xc), _signals.dtype_code(xc),
+                    rows, length, length, out,
+                    what=f'signal_power(shape={tuple(x.shape)}, axis={axis})')
     if keepdims:
         return out.reshape([1 if a in reduced else x.shape[a] for a in range(nd)])
     return out.reshape(kept_shape)
@@ -162,12 +159,9 @@ def input_sxr(
     if B:
         if K == 0 or D == 0 or T == 0:
             raise ValueError(f'empty signal: shape {shape}')
-        dev = x.device.index
-        rc = _lib.load().pbbss_input_sxr(
-            _lib.handle(dev), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(n.data_ptr()),
-            _signals.dtype_code(x), B, K, D, T, int(bool(average_sources)),
-            int(bool(average_channels)), _lib.ptr(out), _lib.stream_ptr(dev))
-        _lib.check(rc, f'input_sxr(shape={shape})')
+        _lib.launch('pbbss_input_sxr', x.device, x, n, _signals.dtype_code(x), B, K, D, T,
+                    bool(average_sources), bool(average_channels), out,
+                    what=f'input_sxr(shape={shape})')
     tail = (() if average_sources else (K,)) + (() if average_channels else (D,))
     values = [_signals.result(out[:, m].reshape(batch + tail), like_torch, home) for m in range(3)]
     return _returned(values, return_dict)
@@ -218,12 +212,9 @@ def output_sxr(image_contribution, noise_contribution, average_sources=True,
     if B:
         if K_source == 0 or samples == 0:
             raise ValueError(f'empty signal: shape {shape}')
-        dev = x.device.index
-        rc = _lib.load().pbbss_output_sxr(
-            _lib.handle(dev), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(n.data_ptr()),
-            _signals.dtype_code(x), B, K_source, K_target, samples, int(bool(average_sources)),
-            _lib.ptr(out), _lib.ptr(selection), _lib.ptr(mean), _lib.stream_ptr(dev))
-        _lib.check(rc, f'output_sxr(shape={shape})')
+        _lib.launch('pbbss_output_sxr', x.device, x, n, _signals.dtype_code(x), B, K_source,
+                    K_target, samples, bool(average_sources), out, selection, mean,
+                    what=f'output_sxr(shape={shape})')
     if average_sources:
         values = [mean[:, m].reshape(batch) for m in range(3)]
     else:

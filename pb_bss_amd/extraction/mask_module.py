@@ -176,12 +176,9 @@ def _pointwise(mode, signal, source_axis, sensor_axis, eps=0.0, keepdims=False, 
         g = _geom(axes4, sources=K, sensors=D, x_source_stride=x.stride(k_ax),
                   x_sensor_stride=0 if d_ax is None else x.stride(d_ax),
                   out_source_stride=out.stride(out_axis(k_ax)))
-        rc = _lib.load().pbbss_mask_pointwise(
-            _lib.handle(x.device.index), ctypes.c_void_p(x.data_ptr()),
-            int(x.dtype == t.complex128), mode, ctypes.byref(g), float(eps), _lib.ptr(table),
-            0 if table is None else table.shape[-1], _lib.ptr(out),
-            _lib.stream_ptr(x.device.index))
-        _lib.check(rc, f'mask_pointwise(mode={mode}, shape={tuple(x.shape)})')
+        _lib.launch('pbbss_mask_pointwise', x.device, _lib.view_ptr(x), x.dtype == t.complex128,
+                    mode, g, eps, table, 0 if table is None else table.shape[-1], out,
+                    what=f'mask_pointwise(mode={mode}, shape={tuple(x.shape)})')
     if out_kind == 'bool':
         out = out.view(t.bool)
     if d_ax is not None and keepdims:
@@ -341,12 +338,9 @@ def lorenz_mask(
 
     def launch(x, g, out, status):
         t = _lib.torch()
-        rc = _lib.load().pbbss_mask_lorenz(
-            _lib.handle(x.device.index), ctypes.c_void_p(x.data_ptr()),
-            int(x.dtype == t.complex128), ctypes.byref(g), float(lorenz_fraction), float(high),
-            float(low), _lib.ptr(out), int(out.dtype == t.float64), _lib.ptr(status),
-            _lib.stream_ptr(x.device.index))
-        _lib.check(rc, f'mask_lorenz(shape={tuple(x.shape)})')
+        _lib.launch('pbbss_mask_lorenz', x.device, _lib.view_ptr(x), x.dtype == t.complex128, g,
+                    lorenz_fraction, high, low, out, out.dtype == t.float64, status,
+                    what=f'mask_lorenz(shape={tuple(x.shape)})')
 
     return _threshold(signal, sensor_axis, axis, keepdims, launch)
 
@@ -409,12 +403,9 @@ def quantile_mask(
         rank = (ctypes.c_int64 * Q)(*[s[0] for s in spec])
         gamma = (ctypes.c_double * Q)(*[s[1] for s in spec])
         negative = (ctypes.c_int * Q)(*[int(s[2]) for s in spec])
-        rc = _lib.load().pbbss_mask_quantile(
-            _lib.handle(x.device.index), ctypes.c_void_p(x.data_ptr()),
-            int(x.dtype == t.complex128), ctypes.byref(g), Q, rank, gamma, negative, float(high),
-            float(low), _lib.ptr(out), int(out.dtype == t.float64), _lib.ptr(status),
-            _lib.stream_ptr(x.device.index))
-        _lib.check(rc, f'mask_quantile(shape={tuple(x.shape)}, quantile={quantiles})')
+        _lib.launch('pbbss_mask_quantile', x.device, _lib.view_ptr(x), x.dtype == t.complex128, g,
+                    Q, rank, gamma, negative, high, low, out, out.dtype == t.float64, status,
+                    what=f'mask_quantile(shape={tuple(x.shape)}, quantile={quantiles})')
 
     return _threshold(signal, None, axis, False, launch, targets, may_fail=False)
 

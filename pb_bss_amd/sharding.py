@@ -67,8 +67,7 @@ def init_native_comm(group=None, device_index=None):
     box = [bytes(uid.raw)]
     dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0,
                                group=group)
-    _lib.check(_lib.load().pbbss_comm_create(_lib.handle(device_index), box[0], world, rank),
-               'comm_create')
+    _lib.control('pbbss_comm_create', device_index, box[0], world, rank, what='comm_create')
     _NATIVE_COMM[device_index] = (world, rank, group)
 
 
@@ -86,7 +85,7 @@ def destroy_native_comm(device_index=None):
     if device_index is None:
         device_index = torch.cuda.current_device()
     if _NATIVE_COMM.pop(device_index, None) is not None:
-        _lib.check(_lib.load().pbbss_comm_destroy(_lib.handle(device_index)), 'comm_destroy')
+        _lib.control('pbbss_comm_destroy', device_index, what='comm_destroy')
 
 
 def _native_all_gather(local, num_bins, bin_axis):
@@ -103,10 +102,9 @@ def _native_all_gather(local, num_bins, bin_axis):
     inner = int(np.prod(shape[bin_axis + 1:], dtype=np.int64))
     out_shape = shape[:bin_axis] + [num_bins] + shape[bin_axis + 1:]
     out = torch.empty(out_shape, dtype=x.dtype, device=x.device)
-    rc = _lib.load().pbbss_allgather_masks(
-        _lib.handle(x.device.index), _lib.ptr(x) if x.numel() else None, x.element_size(), outer,
-        num_bins, inner, _lib.ptr(out), _lib.stream_ptr(x.device.index))
-    _lib.check(rc, f'allgather_masks(outer={outer}, bins={num_bins}, inner={inner})')
+    _lib.launch('pbbss_allgather_masks', x.device, _lib.ptr(x) if x.numel() else None,
+                x.element_size(), outer, num_bins, inner, out,
+                what=f'allgather_masks(outer={outer}, bins={num_bins}, inner={inner})')
     return out
 
 

@@ -88,11 +88,8 @@ def filterbank_rows(x, lengths, coef):
     rows, N = x.shape
     n = coef.shape[0]
     out = t.empty((n, rows, N), dtype=t.float64, device=x.device)
-    dev = x.device.index
-    rc = _lib.load().pbbss_gammatone(
-        _lib.handle(dev), _lib.ptr(x), int(x.dtype == t.float64), rows, N, _lib.ptr(lengths), n,
-        _lib.ptr(coef), _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(rc, f'gammatone_filterbank(rows={rows}, N={N}, n={n})')
+    _lib.launch('pbbss_gammatone', x.device, x, x.dtype == t.float64, rows, N, lengths, n, coef,
+                out, what=f'gammatone_filterbank(rows={rows}, N={N}, n={n})')
     return out
 
 
