@@ -547,58 +547,55 @@ __global__ void __launch_bounds__(kEmThreads, 3)
 }
 
 // ------------------------------------------------------------------ host dispatch
-#define PBBSS_DISPATCH_D(D_, ...)    \
-  switch (D_) {                      \
-    case 2: { constexpr int DD = 2; __VA_ARGS__; } break; \
-    case 3: { constexpr int DD = 3; __VA_ARGS__; } break; \
-    case 4: { constexpr int DD = 4; __VA_ARGS__; } break; \
-    case 5: { constexpr int DD = 5; __VA_ARGS__; } break; \
-    case 6: { constexpr int DD = 6; __VA_ARGS__; } break; \
-    case 7: { constexpr int DD = 7; __VA_ARGS__; } break; \
-    case 8: { constexpr int DD = 8; __VA_ARGS__; } break; \
-    default: return PBBSS_ERR_UNSUPPORTED;         \
-  }
-
 static inline int check_launch() {
   return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
+}
+// f(constant D) for the compiled sensor counts, then the launch status
+template <class F>
+static int launch_for_d(int D, F&& f) {
+  return dispatch_range<2, 8>(D, [&](auto d) {
+    f(d);
+    return check_launch();
+  });
 }
 static inline unsigned la_grid(int64_t N) { return (unsigned)((N + kLaWaves - 1) / kLaWaves); }
 
 int launch_heev(const double* a, int64_t N, int D, double* val, double* vec, int32_t* st,
                 hipStream_t s) {
-  PBBSS_DISPATCH_D(D, hipLaunchKernelGGL(heev_kernel<DD>, dim3(la_grid(N)), dim3(kLaThreads), 0,
-                                         s, a, N, val, vec, st));
-  return check_launch();
+  return launch_for_d(D, [&](auto d) {
+    hipLaunchKernelGGL(heev_kernel<d()>, dim3(la_grid(N)), dim3(kLaThreads), 0, s, a, N, val, vec, st);
+  });
 }
 int launch_gev(const double* t, const double* nn, int64_t N, int D, double* w, int32_t* st,
                hipStream_t s) {
-  PBBSS_DISPATCH_D(D, hipLaunchKernelGGL(gev_kernel<DD>, dim3(la_grid(N)), dim3(kLaThreads), 0, s,
-                                         t, nn, N, w, st));
-  return check_launch();
+  return launch_for_d(D, [&](auto d) {
+    hipLaunchKernelGGL(gev_kernel<d()>, dim3(la_grid(N)), dim3(kLaThreads), 0, s, t, nn, N, w, st);
+  });
 }
 int launch_solve(const double* A, const double* Bm, int64_t N, int D, int M, double* x,
                  int32_t* st, hipStream_t s) {
-  PBBSS_DISPATCH_D(D, hipLaunchKernelGGL(solve_kernel<DD>, dim3(la_grid(N)), dim3(kLaThreads), 0,
-                                         s, A, Bm, N, M, x, st));
-  return check_launch();
+  return launch_for_d(D, [&](auto d) {
+    hipLaunchKernelGGL(solve_kernel<d()>, dim3(la_grid(N)), dim3(kLaThreads), 0, s, A, Bm, N, M, x,
+                       st);
+  });
 }
 int launch_mvdr_souden(const double* t, const double* nn, int64_t N, int D, double eps, int mode,
                        double* mat, double* num, double* den, int32_t* st, hipStream_t s) {
-  PBBSS_DISPATCH_D(D, hipLaunchKernelGGL(mvdr_souden_kernel<DD>, dim3(la_grid(N)),
-                                         dim3(kLaThreads), 0, s, t, nn, N, eps, mode, mat, num,
-                                         den, st));
-  return check_launch();
+  return launch_for_d(D, [&](auto d) {
+    hipLaunchKernelGGL(mvdr_souden_kernel<d()>, dim3(la_grid(N)), dim3(kLaThreads), 0, s, t, nn, N,
+                       eps, mode, mat, num, den, st);
+  });
 }
 int launch_mvdr(const double* atf, const double* nn, int64_t N, int D, double* w, int32_t* st,
                 hipStream_t s) {
-  PBBSS_DISPATCH_D(D, hipLaunchKernelGGL(mvdr_kernel<DD>, dim3(la_grid(N)), dim3(kLaThreads), 0,
-                                         s, atf, nn, N, w, st));
-  return check_launch();
+  return launch_for_d(D, [&](auto d) {
+    hipLaunchKernelGGL(mvdr_kernel<d()>, dim3(la_grid(N)), dim3(kLaThreads), 0, s, atf, nn, N, w, st);
+  });
 }
 int launch_ban(const double* w, const double* nn, int64_t N, int D, double* out, hipStream_t s) {
-  PBBSS_DISPATCH_D(D, hipLaunchKernelGGL(ban_kernel<DD>, dim3(la_grid(N)), dim3(kLaThreads), 0, s,
-                                         w, nn, N, out));
-  return check_launch();
+  return launch_for_d(D, [&](auto d) {
+    hipLaunchKernelGGL(ban_kernel<d()>, dim3(la_grid(N)), dim3(kLaThreads), 0, s, w, nn, N, out);
+  });
 }
 int launch_apply(const double* w, const void* x, int x128, int64_t B, int T, int D, double* out,
                  hipStream_t s, int64_t xmod, int64_t b_first) {
@@ -728,12 +725,8 @@ static int launch_psd_variant(const void* x, int64_t B, int T, const double* mas
   size_t lds = Kern::lds_bytes(T);
   if (lds > cfg.lds_limit) return PBBSS_ERR_LDS_CAPACITY;
   auto kfn = psd_kernel<D, K, YS, SPILL>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, kEmThreads, lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  int occ = blocks_per_cu(kfn, kEmThreads, lds);
+  if (occ < 0) return PBBSS_ERR_HIP;
   if (occ < 1) occ = 1;
   int64_t grid = (int64_t)cfg.num_cu * occ;
   if (grid > B) grid = B;
@@ -760,19 +753,6 @@ static int launch_psd_one(const void* x, int64_t B, int T, const double* mask,
                                             out_bstride, cfg, s);
 }
 
-template <int D, typename YS>
-static int launch_psd_k(int K, const void* x, int64_t B, int T, const double* mask,
-                        int64_t mbs, int normalize, double* out, int64_t obs,
-                        const EmLaunchCfg& cfg, hipStream_t s) {
-  switch (K) {
-    case 1: return launch_psd_one<D, 1, YS>(x, B, T, mask, mbs, normalize, out, obs, cfg, s);
-    case 2: return launch_psd_one<D, 2, YS>(x, B, T, mask, mbs, normalize, out, obs, cfg, s);
-    case 3: return launch_psd_one<D, 3, YS>(x, B, T, mask, mbs, normalize, out, obs, cfg, s);
-    case 4: return launch_psd_one<D, 4, YS>(x, B, T, mask, mbs, normalize, out, obs, cfg, s);
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-}
-
 int launch_psd(const void* x, int x128, int64_t B, int T, int D, int K, const double* mask,
                int normalize, double* out, const EmLaunchCfg& cfg, hipStream_t s) {
   // more than 4 sources: chunks of <= 4 classes per launch
@@ -780,13 +760,14 @@ int launch_psd(const void* x, int x128, int64_t B, int T, int D, int K, const do
     int kc = (K - k0 < 4) ? (K - k0) : 4;
     const double* m = mask ? mask + (int64_t)k0 * T : nullptr;
     double* o = out + (int64_t)k0 * D * D * 2;
-    int rc = PBBSS_OK;
-    PBBSS_DISPATCH_D(D, rc = x128 ? launch_psd_k<DD, double>(kc, x, B, T, m, (int64_t)K * T,
-                                                             normalize, o, (int64_t)K * D * D * 2,
-                                                             cfg, s)
-                                  : launch_psd_k<DD, float>(kc, x, B, T, m, (int64_t)K * T,
-                                                            normalize, o, (int64_t)K * D * D * 2,
-                                                            cfg, s));
+    const int rc = dispatch_range<2, 8>(D, [&](auto d) {
+      return dispatch_real(x128, [&](auto y) {
+        return dispatch_range<1, 4>(kc, [&](auto k) {
+          return launch_psd_one<d(), k(), decltype(y)>(x, B, T, m, (int64_t)K * T, normalize, o,
+                                                       (int64_t)K * D * D * 2, cfg, s);
+        });
+      });
+    });
     if (rc != PBBSS_OK) return rc;
   }
   return PBBSS_OK;

@@ -368,18 +368,11 @@ inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / p
 int launch_lcmv(const double* atf, const double* response, const double* noise, int64_t F, int D,
                 int K, double* w, int32_t* st, hipStream_t s) {
   if (K < 1 || K > D) return PBBSS_ERR_INVALID_ARG;
-#define PBBSS_LCMV_CASE(DD)                                                                     \
-  case DD:                                                                                      \
-    hipLaunchKernelGGL(lcmv_kernel<DD>, dim3(blocks(F, kLaWaves)), dim3(kLaThreads), 0, s, atf, \
-                       response, noise, F, K, w, st);                                           \
-    break;
-  switch (D) {
-    PBBSS_LCMV_CASE(2) PBBSS_LCMV_CASE(3) PBBSS_LCMV_CASE(4) PBBSS_LCMV_CASE(5)
-    PBBSS_LCMV_CASE(6) PBBSS_LCMV_CASE(7) PBBSS_LCMV_CASE(8)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_LCMV_CASE
-  return ok_or_hip();
+  return dispatch_range<2, 8>(D, [&](auto d) {
+    hipLaunchKernelGGL(lcmv_kernel<d()>, dim3(blocks(F, kLaWaves)), dim3(kLaThreads), 0, s, atf,
+                       response, noise, F, K, w, st);
+    return ok_or_hip();
+  });
 }
 
 int launch_phase_correction(const double* v, int64_t lead, int64_t rest, int F, int D, int two_d,

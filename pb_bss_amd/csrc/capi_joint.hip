@@ -13,34 +13,17 @@ using pbbss::as_stream, pbbss::copy_d2d, pbbss::embed_shape_ok, pbbss::Carver, p
 // dynamic LDS of the joint kernels for (D, K, T): the EM kernel's own figure + the 64 bytes of the
 // inline aligner's class permutation.  0 outside the compiled range (D = 2..8, K = 1..6): those
 // shapes are refused or take the generic-size path whatever the figure.
-template <int D, int K>
-static size_t joint_lds_dk(int T, int c128) {
-  return (c128 ? pbbss::EmKernel<D, K, double, false>::lds_bytes(T)
-               : pbbss::EmKernel<D, K, float, false>::lds_bytes(T)) + 64;
-}
-template <int D>
-static size_t joint_lds_d(int K, int T, int c128) {
-  switch (K) {
-    case 1: return joint_lds_dk<D, 1>(T, c128);
-    case 2: return joint_lds_dk<D, 2>(T, c128);
-    case 3: return joint_lds_dk<D, 3>(T, c128);
-    case 4: return joint_lds_dk<D, 4>(T, c128);
-    case 5: return joint_lds_dk<D, 5>(T, c128);
-    case 6: return joint_lds_dk<D, 6>(T, c128);
-    default: return 0;
-  }
-}
 static size_t joint_lds_bytes(int D, int K, int T, int c128) {
-  switch (D) {
-    case 2: return joint_lds_d<2>(K, T, c128);
-    case 3: return joint_lds_d<3>(K, T, c128);
-    case 4: return joint_lds_d<4>(K, T, c128);
-    case 5: return joint_lds_d<5>(K, T, c128);
-    case 6: return joint_lds_d<6>(K, T, c128);
-    case 7: return joint_lds_d<7>(K, T, c128);
-    case 8: return joint_lds_d<8>(K, T, c128);
-    default: return 0;
-  }
+  size_t lds = 0;
+  (void)pbbss::dispatch_range<2, 8>(D, [&](auto d) {
+    return pbbss::dispatch_range<1, 6>(K, [&](auto k) {
+      return pbbss::dispatch_real(c128, [&](auto ys) {
+        lds = pbbss::EmKernel<d(), k(), decltype(ys), false>::lds_bytes(T) + 64;
+        return PBBSS_OK;
+      });
+    });
+  });
+  return lds;
 }
 
 // helper blocks of the in-launch spectral finalize of the rotated joint loop (embed_dev.hpp)

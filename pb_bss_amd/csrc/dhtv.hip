@@ -15,6 +15,8 @@
 // Features (unit-norm masks, float64) live in a caller-provided scratch copy in
 // HBM/L2 (K*F*T*8 bytes per utterance); the normalised centroid in LDS.
 #include "dhtv.hpp"
+#include "dispatch.hpp"
+#include "launch_util.hpp"
 #include "pbbss_dev.hpp"
 
 namespace pbbss {
@@ -1253,12 +1255,6 @@ __global__ void __launch_bounds__(256)
   for (int i = 0; i < K; ++i) mapping[(int64_t)i * N + n] = perm[i];
 }
 
-#define PBBSS_PA_SWITCH(K, CASE)                                                               \
-  switch (K) {                                                                                 \
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)                            \
-    default: return PBBSS_ERR_UNSUPPORTED;                                                     \
-  }
-
 int launch_pa_pair(const double* mask, const double* ref, int64_t U, int K, int64_t F, int T,
                    const int64_t* ms, const int64_t* rs, int metric, int optimal, double* scores,
                    int32_t* mapping, int64_t map_F, int64_t map_col0, int32_t* status,
@@ -1269,13 +1265,10 @@ int launch_pa_pair(const double* mask, const double* ref, int64_t U, int K, int6
                scores, mapping, map_F, map_col0, status};
   const int64_t blocks = (U * F + 3) / 4;
   if (blocks > 2147483647LL) return PBBSS_ERR_UNSUPPORTED;
-#define PBBSS_PA_CASE(KK)                                                                      \
-  case KK:                                                                                     \
-    hipLaunchKernelGGL(pa_pair_kernel<KK>, dim3((unsigned)blocks), dim3(256), 0, s, a);       \
-    break;
-  PBBSS_PA_SWITCH(K, PBBSS_PA_CASE)
-#undef PBBSS_PA_CASE
-  return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
+  return dispatch_range<1, kDhtvMaxK>(K, [&](auto k) {
+    hipLaunchKernelGGL(pa_pair_kernel<k()>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
+  });
 }
 
 int launch_pa_compose(int32_t* mapping, int64_t U, int K, int64_t F, hipStream_t s) {
@@ -1290,33 +1283,23 @@ int launch_pa_assign(const double* scores, int64_t N, int K, int optimal, int32_
   if (K < 1 || K > kDhtvMaxK) return PBBSS_ERR_UNSUPPORTED;
   const int64_t blocks = (N + 255) / 256;
   if (blocks > 2147483647LL) return PBBSS_ERR_UNSUPPORTED;
-#define PBBSS_PA_CASE(KK)                                                                      \
-  case KK:                                                                                     \
-    hipLaunchKernelGGL(pa_assign_kernel<KK>, dim3((unsigned)blocks), dim3(256), 0, s, scores,  \
-                       N, optimal, mapping, status);                                           \
-    break;
-  PBBSS_PA_SWITCH(K, PBBSS_PA_CASE)
-#undef PBBSS_PA_CASE
-  return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
+  return dispatch_range<1, kDhtvMaxK>(K, [&](auto k) {
+    hipLaunchKernelGGL(pa_assign_kernel<k()>, dim3((unsigned)blocks), dim3(256), 0, s, scores, N,
+                       optimal, mapping, status);
+    return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
+  });
 }
-#undef PBBSS_PA_SWITCH
 
-// frame-slice kernel: launches when the shape admits it (returns false otherwise)
+// frame-slice kernel of one (K, frames per lane); the status of its launches
 template <int K, int NF>
-static bool slice_launch_one(const double* mask, int64_t U, int F, int T, const int32_t* plan, int P,
-                             int optimal, int metric, double* feat, int32_t* mapping,
-                             int32_t* status, int G, size_t lds, unsigned* ctrl, double* scale,
-                             bool probe, bool features, unsigned spin_limit, hipStream_t s, int* rc) {
+static int slice_launch_one(const double* mask, int64_t U, int F, int T, const int32_t* plan, int P,
+                            int optimal, int metric, double* feat, int32_t* mapping,
+                            int32_t* status, int G, size_t lds, unsigned* ctrl, double* scale,
+                            bool probe, bool features, unsigned spin_limit, hipStream_t s) {
   auto kfn = dhtv_slice_kernel<K, NF, false>;
   auto pfn = dhtv_slice_kernel<K, NF, true>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-      (probe && hipFuncSetAttribute(reinterpret_cast<const void*>(pfn),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-                    hipSuccess)) {
-    *rc = PBBSS_ERR_HIP;
-    return true;
-  }
+  if (!raise_lds_attribute(kfn, lds) || (probe && !raise_lds_attribute(pfn, lds)))
+    return PBBSS_ERR_HIP;
   // row scales on the whole chip -> [probe: every segment at once on P teams per utterance] ->
   // the plan on G workgroups per utterance -> aligned features
   // control words: [4 per utterance][probe: 4 + 1 flag per (utterance, segment)]
@@ -1335,8 +1318,7 @@ static bool slice_launch_one(const double* mask, int64_t U, int F, int T, const 
   if (features)
     hipLaunchKernelGGL(dhtv_features_kernel, dim3((unsigned)rows), dim3(256), 0, s, mask, mapping,
                        scale, K, F, T, feat);
-  *rc = hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
-  return true;
+  return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
 }
 
 static bool launch_slice(const double* mask, int64_t U, int K, int F, int T, const int32_t* plan,
@@ -1361,17 +1343,17 @@ static bool launch_slice(const double* mask, int64_t U, int K, int F, int T, con
     if (2 * (size_t)G * slice_entries(K, F) > (size_t)K * F * T) continue;
     // the probe's P teams per utterance must be co-resident as well (one workgroup per CU)
     const bool probe = want_probe && P <= 64 && (int64_t)G * U * P <= num_cu;
-#define PBBSS_SLICE_CASE(KK, NN)                                                               \
-  if (K == KK && NF == NN)                                                                     \
-    return slice_launch_one<KK, NN>(mask, U, F, T, plan, P, optimal, metric, feat, mapping,    \
-                                    status, G, lds, ctrl, scale, probe, features, spin_limit, s, \
-                                    rc);
-    PBBSS_SLICE_CASE(1, 4) PBBSS_SLICE_CASE(1, 8)
-    PBBSS_SLICE_CASE(2, 4) PBBSS_SLICE_CASE(2, 8)
-    PBBSS_SLICE_CASE(3, 4) PBBSS_SLICE_CASE(3, 8)
-    PBBSS_SLICE_CASE(4, 4)
-    PBBSS_SLICE_CASE(5, 4)
-#undef PBBSS_SLICE_CASE
+    *rc = dispatch_range<1, 5>(K, [&](auto k) {
+      return dispatch_list<4, 8>(NF, [&](auto nf) {
+        if constexpr (k() * nf() <= 24)  // what the loop can reach: NF = 8 up to K = 3
+          return slice_launch_one<k(), nf()>(mask, U, F, T, plan, P, optimal, metric, feat, mapping,
+                                             status, G, lds, ctrl, scale, probe, features,
+                                             spin_limit, s);
+        else
+          return PBBSS_ERR_UNSUPPORTED;
+      });
+    });
+    return true;
   }
   return false;
 }
@@ -1417,37 +1399,20 @@ int launch_dhtv(const double* mask, int64_t U, int K, int F, int T, const int32_
   const bool team = team_buf && G >= 2 * ncb && ctrl_pad + part_bytes <= team_bytes;
   double* part = reinterpret_cast<double*>(static_cast<char*>(team_buf) + ctrl_pad);
   if (team && hipMemsetAsync(ctrl, 0, ctrl_bytes, s) != hipSuccess) return PBBSS_ERR_HIP;
-#define PBBSS_DHTV_CASE(KK)                                                                     \
-  case KK: {                                                                                    \
-    if (team) {                                                                                 \
-      auto kfn = dhtv_team_kernel<KK>;                                                          \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-        return PBBSS_ERR_HIP;                                                                   \
-      hipLaunchKernelGGL(kfn, dim3((unsigned)(U * G)), dim3(kDhtvThreads), lds, s, mask, feat,  \
-                         mapping, plan, P, F, T, optimal, metric, status, G, part, ctrl, spin_limit);   \
-    } else {                                                                                    \
-      auto kfn = dhtv_kernel<KK>;                                                               \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-        return PBBSS_ERR_HIP;                                                                   \
-      hipLaunchKernelGGL(kfn, dim3((unsigned)U), dim3(kDhtvThreads), lds, s, mask, feat,        \
-                         mapping, plan, P, F, T, optimal, metric, status);                        \
-    }                                                                                           \
-  } break;
-  switch (K) {
-    PBBSS_DHTV_CASE(1)
-    PBBSS_DHTV_CASE(2)
-    PBBSS_DHTV_CASE(3)
-    PBBSS_DHTV_CASE(4)
-    PBBSS_DHTV_CASE(5)
-    PBBSS_DHTV_CASE(6)
-    PBBSS_DHTV_CASE(7)
-    PBBSS_DHTV_CASE(8)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_DHTV_CASE
-  return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
+  return dispatch_range<1, kDhtvMaxK>(K, [&](auto k) {
+    if (team) {
+      auto kfn = dhtv_team_kernel<k()>;
+      if (!raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
+      hipLaunchKernelGGL(kfn, dim3((unsigned)(U * G)), dim3(kDhtvThreads), lds, s, mask, feat,
+                         mapping, plan, P, F, T, optimal, metric, status, G, part, ctrl, spin_limit);
+    } else {
+      auto kfn = dhtv_kernel<k()>;
+      if (!raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
+      hipLaunchKernelGGL(kfn, dim3((unsigned)U), dim3(kDhtvThreads), lds, s, mask, feat, mapping,
+                         plan, P, F, T, optimal, metric, status);
+    }
+    return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
+  });
 }
 
 int launch_apply_mapping(const double* mask, const int32_t* mapping, int64_t U, int K, int F,

@@ -9,52 +9,27 @@
 
 namespace pbbss {
 
-template <int K>
+template <int D, int K>
 static int launch32(EmArgs a, const EmLaunchCfg& cfg, hipStream_t stream) {
-  using Kern = EmKernel32<PBBSS_EM_D, K>;
+  using Kern = EmKernel32<D, K>;
   const size_t lds = Kern::lds_bytes(a.T);
   if (lds > cfg.lds_limit) return PBBSS_ERR_LDS_CAPACITY;  // no HBM-scratch variant of this kernel
-  auto kfn = cacgmm_em32_kernel<PBBSS_EM_D, K>;
-  if (!raise_lds_attribute(reinterpret_cast<const void*>(kfn), lds)) return PBBSS_ERR_HIP;
-  static thread_local size_t cached_lds = 0;
-  static thread_local int cached_occ = 0, cached_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (cached_lds != lds || cached_dev != dev) {
-    int q = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kfn, kEmThreads, lds) != hipSuccess)
-      return PBBSS_ERR_HIP;
-    cached_occ = q < 1 ? 1 : q;
-    cached_lds = lds;
-    cached_dev = dev;
-  }
-  const int occ = cached_occ;
-  // Remainder problems (B = m * CUs + r, small r: the 513th bin of an utterance) as split groups:
-  // G member workgroups per problem, each with a window of frames, in the SAME grid behind the
-  // full workgroups -- they need a free occupancy slot next to them.
-  const int64_t r = a.B % cfg.num_cu;
-  const int window = cfg.split_window > 256 ? 256 : cfg.split_window;
-  const int G = (a.T + window - 1) / window;
-  const size_t slab_need = 256 + Kern::Base::split_slab_doubles((int)r, G) * sizeof(double);
-  const bool split = cfg.allow_split && a.iterations >= kSplitMinIterations && a.B > cfg.num_cu && r >= 1 &&
-                     r <= kSplitMaxProblems && a.T >= 2 * cfg.split_window &&
-                     slab_need <= cfg.xbuf_bytes &&
-                     (a.B - r) <= (int64_t)cfg.num_cu * (occ - 1);
+  auto kfn = cacgmm_em32_kernel<D, K>;
+  int occ = blocks_per_cu(kfn, kEmThreads, lds);
+  if (occ < 0) return PBBSS_ERR_HIP;
+  if (occ < 1) occ = 1;
+  // Remainder problems as split groups (em_launch.hpp), here in the SAME grid behind the full
+  // workgroups -- they need a free occupancy slot next to them.
+  const SplitRule rule{kSplitMinIterations, kSplitNoLimit, (int64_t)cfg.num_cu * (occ - 1), false,
+                       false};
+  const SplitPlan p = plan_split(a, cfg, rule, Kern::Base::split_slab_doubles);
   int64_t grid = (int64_t)cfg.num_cu * occ;
-  if (split) {
-    a.B -= r;
+  if (p.ok) {
+    a.B -= p.r;
     if (grid > a.B) grid = a.B;
     a.main_grid = (int)grid;
-    grid += r * G;
-    a.T_total = a.T;
-    a.split_groups = G;
-    a.split_window = window;
-    a.split_prio = cfg.split_prio32;
-    a.b_first = a.B;
-    a.xcount = reinterpret_cast<unsigned*>(cfg.xbuf);
-    a.xerror = reinterpret_cast<int*>(cfg.xbuf + 128);
-    a.xslab = reinterpret_cast<double*>(cfg.xbuf + 256);
-    a.xepoch = next_split_epoch(cfg);
+    grid += (int64_t)p.r * p.G;
+    stamp_split(a, cfg, p, a.B, cfg.split_prio32);
   } else if (grid > a.B) {
     grid = a.B;
   }
@@ -69,20 +44,10 @@ static int launch32(EmArgs a, const EmLaunchCfg& cfg, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
 }
 
-#define PBBSS_CAT2(a, b) a##b
-#define PBBSS_CAT(a, b) PBBSS_CAT2(a, b)
-
-int PBBSS_CAT(em32_launch_d, PBBSS_EM_D)(int K, const EmArgs& a, const EmLaunchCfg& cfg,
-                                         hipStream_t stream) {
-  switch (K) {
-    case 1: return launch32<1>(a, cfg, stream);
-    case 2: return launch32<2>(a, cfg, stream);
-    case 3: return launch32<3>(a, cfg, stream);
-    case 4: return launch32<4>(a, cfg, stream);
-    case 5: return launch32<5>(a, cfg, stream);
-    case 6: return launch32<6>(a, cfg, stream);
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
+template <int D>
+int em32_launch_d(int K, const EmArgs& a, const EmLaunchCfg& cfg, hipStream_t stream) {
+  return dispatch_range<1, 6>(K, [&](auto k) { return launch32<D, k()>(a, cfg, stream); });
 }
+template int em32_launch_d<PBBSS_EM_D>(int, const EmArgs&, const EmLaunchCfg&, hipStream_t);
 
 }  // namespace pbbss

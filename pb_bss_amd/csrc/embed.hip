@@ -18,6 +18,8 @@
 #include <cmath>
 #include "pbbss_dev.hpp"
 #include "embed_dev.hpp"
+#include "dispatch.hpp"
+#include "launch_util.hpp"
 
 namespace pbbss {
 namespace {
@@ -1678,15 +1680,10 @@ template <int KIND, typename TS>
 int estep_k(int K, const void* yd, int64_t B, int64_t N, int E, const double* mean,
             const double* prec, const double* offset, const double* weight, double out_scale,
             int64_t Tin, double* out_lp, double* out_aff, hipStream_t s) {
-#define PBBSS_ESTEP_CASE(KK) \
-  case KK: return estep_go<KIND, KK, TS>(yd, B, N, E, mean, prec, offset, weight, out_scale, Tin, out_lp, out_aff, s);
-  switch (K) {
-    PBBSS_ESTEP_CASE(1) PBBSS_ESTEP_CASE(2) PBBSS_ESTEP_CASE(3)
-    PBBSS_ESTEP_CASE(4) PBBSS_ESTEP_CASE(5) PBBSS_ESTEP_CASE(6)
-    PBBSS_ESTEP_CASE(7) PBBSS_ESTEP_CASE(8)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_ESTEP_CASE
+  return dispatch_range<1, 8>(K, [&](auto k) {
+    return estep_go<KIND, k(), TS>(yd, B, N, E, mean, prec, offset, weight, out_scale, Tin, out_lp,
+                                   out_aff, s);
+  });
 }
 
 // ---------------------------------------------------------------- diagonal Gaussian E-step
@@ -1852,15 +1849,11 @@ int fit_k(int K, int kind, const void* yr, int64_t B, int64_t N, int E, const do
           double* out_mean, double* out_scale, double* out_weight, double* out_offset,
           double* out_prec, int single_pass, const double* rowscale, hipStream_t s,
           const PartialReduce* reduce) {
-#define PBBSS_FIT_CASE(KK) \
-  case KK: return fit_go<KK, TS>(kind, yr, B, N, E, aff, Tin, sal, cmin, cmax, weight_mode, part, out_mean, out_scale, out_weight, out_offset, out_prec, single_pass, rowscale, s, reduce);
-  switch (K) {
-    PBBSS_FIT_CASE(1) PBBSS_FIT_CASE(2) PBBSS_FIT_CASE(3)
-    PBBSS_FIT_CASE(4) PBBSS_FIT_CASE(5) PBBSS_FIT_CASE(6)
-    PBBSS_FIT_CASE(7) PBBSS_FIT_CASE(8)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_FIT_CASE
+  return dispatch_range<1, 8>(K, [&](auto k) {
+    return fit_go<k(), TS>(kind, yr, B, N, E, aff, Tin, sal, cmin, cmax, weight_mode, part, out_mean,
+                           out_scale, out_weight, out_offset, out_prec, single_pass, rowscale, s,
+                           reduce);
+  });
 }
 }  // namespace
 
@@ -1961,26 +1954,18 @@ int launch_vmf_em(const void* y, int y_is_f64, int64_t B, int64_t N, int E, int 
   // vector boundary, the tile base is R-row aligned) and a 16-byte aligned array
   const int vw = y_is_f64 ? 2 : 4;
   const bool vec = (E % vw == 0) && (reinterpret_cast<uintptr_t>(y) % 16 == 0);
-#define PBBSS_VMF_GO(KK, TT, VV)                                                                  \
-  hipLaunchKernelGGL((vmf_em_kernel<KK, TT, VV>), grid, dim3(kFusedThreads), p.lds, s,            \
-                     static_cast<const TT*>(y), N, E, p.R, p.C, p.L, gamma, mean, prec, offset,   \
-                     weight, sal, part, out_aff)
-#define PBBSS_VMF_EM(KK)                                                                          \
-  case KK:                                                                                        \
-    if (y_is_f64) {                                                                               \
-      if (vec) PBBSS_VMF_GO(KK, double, true); else PBBSS_VMF_GO(KK, double, false);              \
-    } else {                                                                                      \
-      if (vec) PBBSS_VMF_GO(KK, float, true); else PBBSS_VMF_GO(KK, float, false);                \
-    }                                                                                             \
-    break;
-  switch (K) {
-    PBBSS_VMF_EM(1) PBBSS_VMF_EM(2) PBBSS_VMF_EM(3) PBBSS_VMF_EM(4) PBBSS_VMF_EM(5) PBBSS_VMF_EM(6)
-    PBBSS_VMF_EM(7) PBBSS_VMF_EM(8)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_VMF_EM
-#undef PBBSS_VMF_GO
-  if (hipGetLastError() != hipSuccess) return PBBSS_ERR_HIP;
+  const int rc = dispatch_range<1, 8>(K, [&](auto k) {
+    return dispatch_real(y_is_f64, [&](auto t) {
+      return dispatch_bool(vec, [&](auto v) {
+        using TT = decltype(t);
+        hipLaunchKernelGGL((vmf_em_kernel<k(), TT, v()>), grid, dim3(kFusedThreads), p.lds, s,
+                           static_cast<const TT*>(y), N, E, p.R, p.C, p.L, gamma, mean, prec, offset,
+                           weight, sal, part, out_aff);
+        return ok_or_hip();
+      });
+    });
+  });
+  if (rc != PBBSS_OK) return rc;
   if (!accumulate) return PBBSS_OK;  // predict only: the partials are not used
   const size_t Wv = (size_t)K * (E + 1);
   const size_t lds_fin = (Wv + (Wv < (size_t)kFinThreads ? (kFinThreads / Wv) * Wv : 0)) * sizeof(double);
@@ -2011,29 +1996,17 @@ int launch_vmf_bin_em(const void* y, int y_is_f64, int64_t B, int64_t N, int E, 
   const size_t lds = vmf_bin_lds_bytes(N, E, K, y_is_f64);
   if (lds == 0 || lds > lds_limit || K < 1 || K > kEmbedMaxK || B > 2147483647LL)
     return PBBSS_ERR_UNSUPPORTED;
-#define PBBSS_VB_GO(KK, TT)                                                                        \
-  {                                                                                                \
-    auto kfn = vmf_bin_em_kernel<KK, TT>;                                                          \
-    if (lds > 64 * 1024 &&                                                                         \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                                    \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)   \
-      return PBBSS_ERR_HIP;                                                                        \
-    hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(kFusedThreads), lds, s,                        \
-                       static_cast<const TT*>(y), N, E, iterations, gamma, sal, in_mean, in_conc,  \
-                       in_weight, cmin, cmax, weight_mode, mean, conc, weight, out_aff);           \
-  }
-#define PBBSS_VB_K(KK)                                                                             \
-  case KK:                                                                                         \
-    if (y_is_f64) PBBSS_VB_GO(KK, double) else PBBSS_VB_GO(KK, float)                              \
-    break;
-  switch (K) {
-    PBBSS_VB_K(1) PBBSS_VB_K(2) PBBSS_VB_K(3) PBBSS_VB_K(4) PBBSS_VB_K(5) PBBSS_VB_K(6)
-    PBBSS_VB_K(7) PBBSS_VB_K(8)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_VB_K
-#undef PBBSS_VB_GO
-  return ok_or_hip();
+  return dispatch_range<1, 8>(K, [&](auto k) {
+    return dispatch_real(y_is_f64, [&](auto t) {
+      using TT = decltype(t);
+      auto kfn = vmf_bin_em_kernel<k(), TT>;
+      if (lds > 64 * 1024 && !raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
+      hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(kFusedThreads), lds, s,
+                         static_cast<const TT*>(y), N, E, iterations, gamma, sal, in_mean, in_conc,
+                         in_weight, cmin, cmax, weight_mode, mean, conc, weight, out_aff);
+      return ok_or_hip();
+    });
+  });
 }
 
 // ---- rotated joint loop: sweep (posteriors + spectral sums) and its finalize -------------------
@@ -2116,49 +2089,37 @@ int launch_joint_sweep(int kind, const void* y, int y_is_f64, int64_t F, int T, 
                         ((size_t)(kFusedThreads / kWave) * K * E + 2 * (size_t)(kFusedThreads / kWave) * K) * 8;
     if (!wave_off && !y_is_f64 && E % 4 == 0 && E >= 4 && E <= 64 && K >= 2 && K <= 4 &&
         reinterpret_cast<uintptr_t>(y) % 16 == 0 && p.L % kWave == 0 && wlds <= 64 * 1024) {
-#define PBBSS_JW_GO(KIND, KK, NU)                                                                  \
-  hipLaunchKernelGGL((joint_sweep_wave_kernel<KIND, KK, NU>), grid, dim3(kFusedThreads), wlds, s,  \
-                     static_cast<const float*>(y), N, E, p.L, T, D, Q, lndet, weight, wb, wk, wt,  \
-                     mean, prec, offset, spatial_weight, spectral_weight, sal, eps, G, part, part2)
-#define PBBSS_JW_N(KIND, KK)                                                                       \
-  if (E <= 40) PBBSS_JW_GO(KIND, KK, 10); else PBBSS_JW_GO(KIND, KK, 16)
-#define PBBSS_JW_K(KK)                                                                             \
-  case KK:                                                                                         \
-    if (gauss) { PBBSS_JW_N(PBBSS_EMBED_GAUSS_SPHERICAL, KK); } else { PBBSS_JW_N(PBBSS_EMBED_VMF, KK); } \
-    break;
-      switch (K) { PBBSS_JW_K(2) PBBSS_JW_K(3) PBBSS_JW_K(4) }
-#undef PBBSS_JW_K
-#undef PBBSS_JW_N
-#undef PBBSS_JW_GO
-      return ok_or_hip();
+      return dispatch_range<2, 4>(K, [&](auto k) {
+        return dispatch_bool(gauss, [&](auto g) {
+          return dispatch_list<10, 16>(E <= 40 ? 10 : 16, [&](auto nu) {
+            constexpr int KIND = g() ? PBBSS_EMBED_GAUSS_SPHERICAL : PBBSS_EMBED_VMF;
+            hipLaunchKernelGGL((joint_sweep_wave_kernel<KIND, k(), nu()>), grid,
+                               dim3(kFusedThreads), wlds, s, static_cast<const float*>(y), N, E, p.L,
+                               T, D, Q, lndet, weight, wb, wk, wt, mean, prec, offset,
+                               spatial_weight, spectral_weight, sal, eps, G, part, part2);
+            return ok_or_hip();
+          });
+        });
+      });
     }
   }
   const int vw = y_is_f64 ? 2 : 4;
   const bool vec = (E % vw == 0) && (reinterpret_cast<uintptr_t>(y) % 16 == 0);
-#define PBBSS_JS_GO(KIND, KK, TT, VV)                                                              \
-  hipLaunchKernelGGL((joint_sweep_kernel<KIND, KK, TT, VV>), grid, dim3(kFusedThreads), p.lds, s,  \
-                     static_cast<const TT*>(y), N, E, p.R, p.C, p.L, T, D, Q, lndet, weight, wb,   \
-                     wk, wt, mean, prec, offset, spatial_weight, spectral_weight, sal, eps, G,     \
-                     part, part2)
-#define PBBSS_JS_T(KIND, KK)                                                                       \
-  if (y_is_f64) {                                                                                  \
-    if (vec) PBBSS_JS_GO(KIND, KK, double, true); else PBBSS_JS_GO(KIND, KK, double, false);       \
-  } else {                                                                                         \
-    if (vec) PBBSS_JS_GO(KIND, KK, float, true); else PBBSS_JS_GO(KIND, KK, float, false);         \
-  }
-#define PBBSS_JS_K(KK)                                                                             \
-  case KK:                                                                                         \
-    if (gauss) { PBBSS_JS_T(PBBSS_EMBED_GAUSS_SPHERICAL, KK) } else { PBBSS_JS_T(PBBSS_EMBED_VMF, KK) } \
-    break;
-  switch (K) {
-    PBBSS_JS_K(1) PBBSS_JS_K(2) PBBSS_JS_K(3) PBBSS_JS_K(4) PBBSS_JS_K(5) PBBSS_JS_K(6)
-    PBBSS_JS_K(7) PBBSS_JS_K(8)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_JS_K
-#undef PBBSS_JS_T
-#undef PBBSS_JS_GO
-  return ok_or_hip();
+  return dispatch_range<1, 8>(K, [&](auto k) {
+    return dispatch_bool(gauss, [&](auto g) {
+      return dispatch_real(y_is_f64, [&](auto t) {
+        return dispatch_bool(vec, [&](auto v) {
+          constexpr int KIND = g() ? PBBSS_EMBED_GAUSS_SPHERICAL : PBBSS_EMBED_VMF;
+          using TT = decltype(t);
+          hipLaunchKernelGGL((joint_sweep_kernel<KIND, k(), TT, v()>), grid, dim3(kFusedThreads),
+                             p.lds, s, static_cast<const TT*>(y), N, E, p.R, p.C, p.L, T, D, Q,
+                             lndet, weight, wb, wk, wt, mean, prec, offset, spatial_weight,
+                             spectral_weight, sal, eps, G, part, part2);
+          return ok_or_hip();
+        });
+      });
+    });
+  });
 }
 
 // the model of the spectral half from the sweep's partials (+ the constants the next sweep

@@ -34,6 +34,7 @@
 #include <cmath>
 #include "pbbss_dev.hpp"
 #include "embed_dev.hpp"
+#include "dispatch.hpp"
 
 namespace pbbss {
 namespace {
@@ -718,15 +719,11 @@ int launch_wide_sweep(const Sweep& q, const WidePlan& p, const WideWork& w, size
   a.mu_lds = fixed + mu <= limit;
   const size_t lds = fixed + (a.mu_lds ? mu : 0);
   dim3 grid((unsigned)p.C, (unsigned)q.B, (unsigned)(q.accumulate ? p.FS : 1));
-#define PBBSS_WIDE_CASE(KT)                                                   \
-  case KT:                                                                    \
-    return q.y_is_f64 ? sweep_go<double, KT>(a, q.nm, p.ETW, grid, lds, s)     \
-                      : sweep_go<float, KT>(a, q.nm, p.ETW, grid, lds, s);
-  switch (p.KT) {
-    PBBSS_WIDE_CASE(1) PBBSS_WIDE_CASE(2) PBBSS_WIDE_CASE(3) PBBSS_WIDE_CASE(4)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_WIDE_CASE
+  return dispatch_range<1, 4>(p.KT, [&](auto kt) {
+    return dispatch_real(q.y_is_f64, [&](auto ys) {
+      return sweep_go<decltype(ys), kt()>(a, q.nm, p.ETW, grid, lds, s);
+    });
+  });
 }
 
 int launch_wide_finalize(int kind, int64_t B, int E, int K, const WidePlan& p, const WideWork& w,

@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "gauss_full.hpp"
+#include "dispatch.hpp"
+#include "launch_util.hpp"
 #include "pbbss_dev.hpp"
 
 namespace pbbss {
@@ -621,9 +623,7 @@ int gf_fit_go(const void* y, int64_t B, int64_t N, int E, int K, const double* w
   if (out_mq && 2 * (size_t)E * (E + 1) > ldsd) ldsd = 2 * (size_t)E * (E + 1);
   const size_t lds = ldsd * sizeof(double);
   auto kfn = gf_finalize_kernel<NT, TS>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (!raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
   double* gsum = part + (size_t)B * K * C * NTT * 256;  // behind the workgroup partials
   hipLaunchKernelGGL(gf_reduce_kernel, dim3((unsigned)NTT, (unsigned)K, (unsigned)B),
                      dim3(kGfThreads), 0, s, part, C, NTT, K, gsum);
@@ -654,9 +654,7 @@ int gf_logpdf_go(const void* y, int64_t B, int64_t N, int E, int K, const double
       ((size_t)KC * P * (P + 1) + (size_t)K * 64 * groups + (size_t)KC * (2 * P + 1)) *
       sizeof(double);
   auto kfn = gf_logpdf_kernel<NT, TS>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (!raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
   const int64_t per = 64 * (int64_t)groups;
   hipLaunchKernelGGL(kfn, dim3((unsigned)((N + per - 1) / per), (unsigned)B), dim3(kGfThreads),
                      lds, s, static_cast<const TS*>(y), N, E, K, KC, groups, mean, mq, offset,
@@ -672,14 +670,13 @@ size_t gauss_full_partial_doubles(int64_t B, int64_t N, int E, int K) {
   return (size_t)B * K * (C + 1) * (size_t)(NT * (NT + 1) / 2) * 256;  // + tile sums
 }
 
-#define PBBSS_GF_DISPATCH(FN, ...)                                                      \
-  switch ((E + 1 + 15) / 16) {                                                          \
-    case 1: return y_is_f64 ? FN<1, double>(__VA_ARGS__) : FN<1, float>(__VA_ARGS__);   \
-    case 2: return y_is_f64 ? FN<2, double>(__VA_ARGS__) : FN<2, float>(__VA_ARGS__);   \
-    case 3: return y_is_f64 ? FN<3, double>(__VA_ARGS__) : FN<3, float>(__VA_ARGS__);   \
-    case 4: return y_is_f64 ? FN<4, double>(__VA_ARGS__) : FN<4, float>(__VA_ARGS__);   \
-    default: return PBBSS_ERR_UNSUPPORTED;                                              \
-  }
+// f(tiles of 16 columns covering E + 1 as a constant, the storage type)
+template <class F>
+static int gf_dispatch(int E, int y_is_f64, F&& f) {
+  return dispatch_range<1, 4>((E + 1 + 15) / 16, [&](auto nt) {
+    return dispatch_real(y_is_f64, [&](auto ts) { return f(nt, ts); });
+  });
+}
 
 int launch_gauss_full_fit(const void* y, int y_is_f64, int64_t B, int64_t N, int E, int K,
                           const double* weights, const double* sal, double* part,
@@ -689,8 +686,10 @@ int launch_gauss_full_fit(const void* y, int y_is_f64, int64_t B, int64_t N, int
   if (E < 1 || E > kGaussFullMaxE || K < 1 || B < 1 || B > 65535 || K > 65535)
     return PBBSS_ERR_UNSUPPORTED;
   if ((shift || reduce) && B != 1) return PBBSS_ERR_INVALID_ARG;  // one mixture over the ranks
-  PBBSS_GF_DISPATCH(gf_fit_go, y, B, N, E, K, weights, sal, part, out_mean, out_cov, out_mq,
-                    out_offset, out_s0, out_status, s, shift, reduce)
+  return gf_dispatch(E, y_is_f64, [&](auto nt, auto ts) {
+    return gf_fit_go<nt(), decltype(ts)>(y, B, N, E, K, weights, sal, part, out_mean, out_cov,
+                                         out_mq, out_offset, out_s0, out_status, s, shift, reduce);
+  });
 }
 
 int launch_gauss_full_weights(const double* s0, int64_t B, int K, int mode, double* out_weight,
@@ -715,8 +714,10 @@ int launch_gauss_full_logpdf(const void* y, int y_is_f64, int64_t B, int64_t N, 
                              hipStream_t s) {
   if (E < 1 || E > kGaussFullMaxE || K < 1 || K > 64 || B > 65535) return PBBSS_ERR_UNSUPPORTED;
   if (out_aff && !weight) return PBBSS_ERR_INVALID_ARG;
-  PBBSS_GF_DISPATCH(gf_logpdf_go, y, B, N, E, K, mean, mq, offset, weight, out_lp, out_aff, s)
+  return gf_dispatch(E, y_is_f64, [&](auto nt, auto ts) {
+    return gf_logpdf_go<nt(), decltype(ts)>(y, B, N, E, K, mean, mq, offset, weight, out_lp,
+                                            out_aff, s);
+  });
 }
-#undef PBBSS_GF_DISPATCH
 
 }  // namespace pbbss

@@ -22,6 +22,8 @@
 #include "generic.hpp"
 #include <cmath>
 #include "generic_dev.hpp"
+#include "dispatch.hpp"
+#include "launch_util.hpp"
 #include "prescale.hpp"
 #include <cstdlib>
 #include <type_traits>
@@ -1141,9 +1143,7 @@ inline int ok_or_hip() { return hipGetLastError() == hipSuccess ? PBBSS_OK : PBB
 template <typename KFN>
 int set_lds(KFN kfn, size_t lds, size_t lds_limit) {
   if (lds > lds_limit) return PBBSS_ERR_LDS_CAPACITY;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (!raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
   return PBBSS_OK;
 }
 
@@ -1169,22 +1169,14 @@ int launch_gen_estep(const void* y, int y_is_c128, int layout, int64_t B, int T,
   const dim3 grid((unsigned)B, (unsigned)((T + kGenThreads - 1) / kGenThreads));
   if (grid.y > 65535u) return PBBSS_ERR_UNSUPPORTED;
   const size_t lds = (size_t)2 * K * kGenThreads * sizeof(double);  // softmax slots [2][K][thread]
-#define PBBSS_GEN_E(DPV, YST)                                                              \
-  {                                                                                        \
-    auto kfn = gen_estep_kernel<DPV, YST>;                                                 \
-    if (lds > 32768 && set_lds(kfn, lds, 131072) != PBBSS_OK) return PBBSS_ERR_HIP;        \
-    hipLaunchKernelGGL(kfn, grid, dim3(kGenThreads), lds, s, a);                           \
-  }
-#define PBBSS_GEN_ED(DPV) \
-  case DPV: if (y_is_c128) { PBBSS_GEN_E(DPV, double) } else { PBBSS_GEN_E(DPV, float) } break;
-  switch (DP) {
-    PBBSS_GEN_ED(12) PBBSS_GEN_ED(16) PBBSS_GEN_ED(20) PBBSS_GEN_ED(24) PBBSS_GEN_ED(28)
-    PBBSS_GEN_ED(32) PBBSS_GEN_ED(36)
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
-#undef PBBSS_GEN_ED
-#undef PBBSS_GEN_E
-  return ok_or_hip();
+  return dispatch_list<12, 16, 20, 24, 28, 32, 36>(DP, [&](auto dp) {
+    return dispatch_real(y_is_c128, [&](auto ys) {
+      auto kfn = gen_estep_kernel<dp(), decltype(ys)>;
+      if (lds > 32768 && set_lds(kfn, lds, 131072) != PBBSS_OK) return PBBSS_ERR_HIP;
+      hipLaunchKernelGGL(kfn, grid, dim3(kGenThreads), lds, s, a);
+      return ok_or_hip();
+    });
+  });
 }
 
 int launch_gen_cov(const void* y, int y_is_c128, int layout, int64_t B, int T, int D, int K,
@@ -1196,33 +1188,27 @@ int launch_gen_cov(const void* y, int y_is_c128, int layout, int64_t B, int T, i
   const int DP = D <= 16 ? 16 : (D <= 32 ? 32 : 36);
   const size_t lds = (gen_cov_stage_doubles(DP) + (size_t)kCovMaxK * kTile +
                       (size_t)kGenMaxK * kTile + kGenMaxK) * sizeof(double);
-  int rc;
-#define PBBSS_GEN_C(DPV, KMV, YST)                                                         \
-  {                                                                                        \
-    auto kfn = gen_cov_kernel<DPV, KMV, YST>;                                              \
-    if ((rc = set_lds(kfn, lds, lds_limit)) != PBBSS_OK) return rc;                        \
-    hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(kGenThreads), lds, s, a);              \
-  }
-#define PBBSS_GEN_CK(DPV, YST) \
-  if (kc <= 3) PBBSS_GEN_C(DPV, 3, YST) else PBBSS_GEN_C(DPV, kCovMaxK, YST)
   // balanced chunks of at most kCovMaxK classes, e.g. K = 9 -> 5 + 4, K = 7 -> 4 + 3
   const int nchunk = (K + kCovMaxK - 1) / kCovMaxK;
   for (int c = 0, k0 = 0; c < nchunk; ++c) {
     const int kc = (K - k0 + (nchunk - c) - 1) / (nchunk - c);
     GenCov a{y, layout, B, T, D, K, gamma, gamma_bstride, q, saliency, mode, weight_mode,
              out_cov, out_weight, out_sum, out_zero, k0, kc};
-    if (DP == 16) {
-      if (y_is_c128) { PBBSS_GEN_CK(16, double) } else { PBBSS_GEN_CK(16, float) }
-    } else if (DP == 32) {
-      if (y_is_c128) { PBBSS_GEN_CK(32, double) } else { PBBSS_GEN_CK(32, float) }
-    } else {
-      if (y_is_c128) { PBBSS_GEN_CK(36, double) } else { PBBSS_GEN_CK(36, float) }
-    }
+    const int rc = dispatch_list<16, 32, 36>(DP, [&](auto dp) {
+      return dispatch_real(y_is_c128, [&](auto ys) {
+        return dispatch_list<3, kCovMaxK>(kc <= 3 ? 3 : kCovMaxK, [&](auto km) {
+          auto kfn = gen_cov_kernel<dp(), km(), decltype(ys)>;
+          const int rl = set_lds(kfn, lds, lds_limit);
+          if (rl != PBBSS_OK) return rl;
+          hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(kGenThreads), lds, s, a);
+          return ok_or_hip();
+        });
+      });
+    });
+    if (rc != PBBSS_OK) return rc;
     k0 += kc;
   }
-#undef PBBSS_GEN_CK
-#undef PBBSS_GEN_C
-  return ok_or_hip();
+  return PBBSS_OK;
 }
 
 namespace {
@@ -1475,39 +1461,30 @@ int launch_gen_heev(const double* a, int64_t N, int D, int covariance_norm, doub
   if (D < 2 || D > kGenMaxDEm) return PBBSS_ERR_UNSUPPORTED;
   GenHeev g{a, N, D, covariance_norm, eig_floor, out_val, out_vec, out_status, skip};
   const int DP = D <= 16 ? 16 : (D <= 24 ? 24 : (D <= 32 ? 32 : 36));
-  int rc;
   static const bool use_jacobi = [] {
     const char* v = getenv("PBBSS_GEN_HEEV");
     return v && v[0] == 'j';
   }();
   if (!use_jacobi || D > kGenMaxD) {  // tridiagonal QL, one wavefront per matrix (the only solver beyond 32)
     const size_t lds = ((size_t)D * (D + 1) * 3 + 2 * (DP + 1) + 6 * DP) * sizeof(double);
-#define PBBSS_GEN_Q(DPV)                                                          \
-  {                                                                               \
-    auto kfn = gen_heev_ql_kernel<DPV>;                                           \
-    if ((rc = set_lds(kfn, lds, lds_limit)) != PBBSS_OK) return rc;               \
-    hipLaunchKernelGGL(kfn, dim3((unsigned)N), dim3(kWave), lds, s, g);           \
+    return dispatch_list<16, 24, 32, 36>(DP, [&](auto dp) {
+      auto kfn = gen_heev_ql_kernel<dp()>;
+      const int rl = set_lds(kfn, lds, lds_limit);
+      if (rl != PBBSS_OK) return rl;
+      hipLaunchKernelGGL(kfn, dim3((unsigned)N), dim3(kWave), lds, s, g);
+      return ok_or_hip();
+    });
   }
-    if (DP == 16) PBBSS_GEN_Q(16)
-    else if (DP == 24) PBBSS_GEN_Q(24)
-    else if (DP == 32) PBBSS_GEN_Q(32)
-    else PBBSS_GEN_Q(36)
-#undef PBBSS_GEN_Q
+  return dispatch_list<16, 24, 32>(DP, [&](auto dp) {  // DP * DP threads
+    constexpr int DPV = dp(), NTV = DPV * DPV;
+    const size_t lds = ((size_t)4 * DPV * DPV * 2 + DPV * 3 + NTV / 64) * sizeof(double) +
+                       DPV * sizeof(int);
+    auto kfn = gen_heev_kernel<DPV, NTV>;
+    const int rl = set_lds(kfn, lds, lds_limit);
+    if (rl != PBBSS_OK) return rl;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)N), dim3(NTV), lds, s, g);
     return ok_or_hip();
-  }
-#define PBBSS_GEN_H(DPV, NTV)                                                                  \
-  {                                                                                            \
-    const size_t lds = ((size_t)4 * DPV * DPV * 2 + DPV * 3 + NTV / 64) * sizeof(double) +    \
-                       DPV * sizeof(int);                                                      \
-    auto kfn = gen_heev_kernel<DPV, NTV>;                                                      \
-    if ((rc = set_lds(kfn, lds, lds_limit)) != PBBSS_OK) return rc;                            \
-    hipLaunchKernelGGL(kfn, dim3((unsigned)N), dim3(NTV), lds, s, g);                          \
-  }
-  if (DP == 16) PBBSS_GEN_H(16, 256)
-  else if (DP == 24) PBBSS_GEN_H(24, 576)
-  else PBBSS_GEN_H(32, 1024)
-#undef PBBSS_GEN_H
-  return ok_or_hip();
+  });
 }
 
 int launch_gen_inverse(const double* a, int64_t N, int D, double eig_floor, double* out_inv,

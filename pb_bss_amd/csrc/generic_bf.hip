@@ -7,6 +7,7 @@
 #include "generic_bf.hpp"
 #include <cmath>
 #include "generic_dev.hpp"
+#include "launch_util.hpp"
 #include "prescale.hpp"
 
 namespace pbbss {
@@ -413,9 +414,7 @@ inline int ok_or_hip() { return hipGetLastError() == hipSuccess ? PBBSS_OK : PBB
 template <typename KFN>
 int prep(KFN kfn, size_t lds_limit) {
   if (kWorkBytes > lds_limit) return PBBSS_ERR_LDS_CAPACITY;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWorkBytes) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (!raise_lds_attribute(kfn, kWorkBytes)) return PBBSS_ERR_HIP;
   return PBBSS_OK;
 }
 
@@ -462,9 +461,7 @@ int launch_gen_gev(const double* t, const double* nn, int64_t N, int D, double* 
                    size_t lds_limit, hipStream_t s) {
   if (D < 2 || D > LD) return PBBSS_ERR_UNSUPPORTED;
   if (kGevBytes > lds_limit) return PBBSS_ERR_LDS_CAPACITY;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(gen_gev_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGevBytes) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (!raise_lds_attribute(gen_gev_kernel, kGevBytes)) return PBBSS_ERR_HIP;
   hipLaunchKernelGGL(gen_gev_kernel, dim3((unsigned)N), dim3(kGenThreads), kGevBytes, s, t, nn, D,
                      w, st);
   return ok_or_hip();

@@ -34,6 +34,7 @@
 #include "initializer.hpp"
 #include <limits>
 #include "generic.hpp"
+#include "launch_util.hpp"
 #include "pbbss.h"
 #include "pbbss_dev.hpp"
 #include "wave_la.hpp"
@@ -317,10 +318,7 @@ template <int DT, typename Y2>
 int launch_bin(const DeflationArgs& a, int init, int phase, bool lds_sal, bool lds_y, size_t lds,
                hipStream_t s) {
   auto kfn = deflation_bin_kernel<DT, Y2>;
-  if (lds > 0 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (lds > 0 && !raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
   hipLaunchKernelGGL(kfn, dim3((unsigned)(a.B * a.F)), dim3(kDsThreads), lds, s, a, init, phase,
                      (int)lds_sal, (int)lds_y);
   return ds_ok();

@@ -18,6 +18,7 @@
 // The data-dependent stop lives on the device: finalize sets the problem's state, and the sweeps
 // and finalizes that the host has already enqueued behind it return at once.
 #include "kmeans.hpp"
+#include "launch_util.hpp"
 
 #include <algorithm>
 
@@ -695,10 +696,7 @@ __global__ void __launch_bounds__(kT)
 template <int KT, typename TS>
 int launch_sweep_kt(const KmeansGeom& g, const SweepArgs& a, hipStream_t s) {
   auto kern = kmeans_sweep_kernel<KT, TS>;
-  if (g.lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (g.lds > 64 * 1024 && !raise_lds_attribute(kern, g.lds)) return PBBSS_ERR_HIP;
   hipLaunchKernelGGL(kern, dim3((unsigned)(g.B * g.C)), dim3(kT), g.lds, s, a);
   return hip_ok();
 }

@@ -12,18 +12,14 @@
 
 namespace pbbss {
 
-template <int K, typename YS>
+template <int D, int K, typename YS>
 static int launch_shared_one(EmArgs a, const EmLaunchCfg& cfg, hipStream_t stream) {
-  using Kern = EmKernel<PBBSS_EM_D, K, YS, false>;
+  using Kern = EmKernel<D, K, YS, false>;
   const size_t lds = Kern::lds_bytes(a.T);
   if (lds > cfg.lds_limit) return PBBSS_ERR_UNSUPPORTED;  // frames must be LDS-resident
-  auto kfn = cacgmm_em_shared_kernel<PBBSS_EM_D, K, YS>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, kEmThreads, lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  auto kfn = cacgmm_em_shared_kernel<D, K, YS>;
+  const int occ = blocks_per_cu(kfn, kEmThreads, lds);  // unclamped: 0 means no group fits
+  if (occ < 0) return PBBSS_ERR_HIP;
   const int64_t capacity = (int64_t)cfg.num_cu * occ;
   if (a.wgroup > capacity) return PBBSS_ERR_UNSUPPORTED;  // a group must be co-resident
   const int64_t ngroups = a.B / a.wgroup;
@@ -62,24 +58,14 @@ static int launch_shared_one(EmArgs a, const EmLaunchCfg& cfg, hipStream_t strea
   return PBBSS_OK;
 }
 
-template <typename YS>
-static int launch_shared_k(int K, const EmArgs& a, const EmLaunchCfg& cfg, hipStream_t stream) {
-  switch (K) {
-    case 1: return launch_shared_one<1, YS>(a, cfg, stream);
-    case 2: return launch_shared_one<2, YS>(a, cfg, stream);
-    case 3: return launch_shared_one<3, YS>(a, cfg, stream);
-    case 4: return launch_shared_one<4, YS>(a, cfg, stream);
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
+template <int D>
+int em_shared_launch_d(int K, int y_is_c128, const EmArgs& a, const EmLaunchCfg& cfg,
+                       hipStream_t stream) {
+  return dispatch_real(y_is_c128, [&](auto y) {
+    return dispatch_range<1, 4>(
+        K, [&](auto k) { return launch_shared_one<D, k(), decltype(y)>(a, cfg, stream); });
+  });
 }
-
-#define PBBSS_CAT2(a, b) a##b
-#define PBBSS_CAT(a, b) PBBSS_CAT2(a, b)
-
-int PBBSS_CAT(em_shared_launch_d, PBBSS_EM_D)(int K, int y_is_c128, const EmArgs& a,
-                                              const EmLaunchCfg& cfg, hipStream_t stream) {
-  return y_is_c128 ? launch_shared_k<double>(K, a, cfg, stream)
-                   : launch_shared_k<float>(K, a, cfg, stream);
-}
+template int em_shared_launch_d<PBBSS_EM_D>(int, int, const EmArgs&, const EmLaunchCfg&, hipStream_t);
 
 }  // namespace pbbss

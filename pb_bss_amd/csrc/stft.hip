@@ -19,6 +19,7 @@
 // HBM traffic is tiny next to the EM loop (one utterance: 3.1 MB out), so the kernels are
 // written for simplicity: the time is launch + LDS-latency bound, a few tens of microseconds.
 #include "stft.hpp"
+#include "launch_util.hpp"
 #include <cmath>
 #include "pbbss_dev.hpp"
 
@@ -249,9 +250,7 @@ int launch_stft(const void* x, int x_is_f64, int64_t C, int64_t N, int size, int
   const int M = size / 2;
   const size_t lds = ((size_t)2 * M + M + 1) * sizeof(Cplx);
   if (lds > lds_limit) return PBBSS_ERR_LDS_CAPACITY;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (!raise_lds_attribute(stft_kernel, lds)) return PBBSS_ERR_HIP;
   StftArgs g{x, x_is_f64, C, N, size, shift, wl, window, fade, T, layout, out_c128, out};
   const dim3 grid((unsigned)((T + kFramesPerWg - 1) / kFramesPerWg), (unsigned)C);
   hipLaunchKernelGGL(stft_kernel, grid, dim3(kStftThreads), lds, s, g);
@@ -267,9 +266,7 @@ int launch_istft(const void* X, int x_is_c128, int64_t C, int T, int size, int s
   const int M = size / 2;
   const size_t lds = ((size_t)2 * M + 2 * (M + 1)) * sizeof(Cplx);
   if (lds > lds_limit) return PBBSS_ERR_LDS_CAPACITY;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(istft_frames_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (!raise_lds_attribute(istft_frames_kernel, lds)) return PBBSS_ERR_HIP;
   IstftArgs g{X, x_is_c128, C, T, size, shift, wl, window, frames};
   const dim3 grid((unsigned)((T + kFramesPerWg - 1) / kFramesPerWg), (unsigned)C);
   hipLaunchKernelGGL(istft_frames_kernel, grid, dim3(kStftThreads), lds, s, g);

@@ -36,6 +36,8 @@
 #include <type_traits>
 #include "pbbss_dev.hpp"
 #include "embed_dev.hpp"
+#include "dispatch.hpp"
+#include "launch_util.hpp"
 
 namespace pbbss {
 namespace {
@@ -410,10 +412,7 @@ int go(const VmfBinArgs& a, int64_t B, size_t lds_limit, hipStream_t s) {
   const size_t lds = Kern::lds_bytes(a.N);
   if (lds > lds_limit) return PBBSS_ERR_UNSUPPORTED;
   auto kfn = vmf_bin_em2_kernel<K, EP, TS, NW>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PBBSS_ERR_HIP;
+  if (lds > 64 * 1024 && !raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
   hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(NW * kWave), lds, s, a);
   return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
 }
@@ -445,13 +444,8 @@ int go_k(const VmfBinArgs& a, int y_is_f64, int64_t B, size_t lds_limit, int num
 template <int K>
 int go_e(const VmfBinArgs& a, int y_is_f64, int64_t B, size_t lds_limit, int num_cu, hipStream_t s) {
   const int EP = (a.E + 3) & ~3;
-  switch (EP) {
-    case 4: return go_k<K, 4>(a, y_is_f64, B, lds_limit, num_cu, s);
-    case 8: return go_k<K, 8>(a, y_is_f64, B, lds_limit, num_cu, s);
-    case 12: return go_k<K, 12>(a, y_is_f64, B, lds_limit, num_cu, s);
-    case 16: return go_k<K, 16>(a, y_is_f64, B, lds_limit, num_cu, s);
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
+  return dispatch_list<4, 8, 12, 16>(
+      EP, [&](auto ep) { return go_k<K, ep()>(a, y_is_f64, B, lds_limit, num_cu, s); });
 }
 
 }  // namespace
@@ -472,12 +466,8 @@ int launch_vmf_bin_em2(const void* y, int y_is_f64, int64_t B, int64_t N, int E,
     return PBBSS_ERR_UNSUPPORTED;
   VmfBinArgs a{y, (int)N, E, iterations, gamma, sal, in_mean, in_conc, in_weight, cmin, cmax,
                weight_mode, mean, conc, weight, out_aff};
-  switch (K) {
-    case 2: return go_e<2>(a, y_is_f64, B, lds_limit, num_cu, s);
-    case 3: return go_e<3>(a, y_is_f64, B, lds_limit, num_cu, s);
-    case 4: return go_e<4>(a, y_is_f64, B, lds_limit, num_cu, s);
-    default: return PBBSS_ERR_UNSUPPORTED;
-  }
+  return dispatch_range<2, 4>(
+      K, [&](auto k) { return go_e<k()>(a, y_is_f64, B, lds_limit, num_cu, s); });
 }
 
 }  // namespace pbbss

@@ -402,6 +402,26 @@ def test_stepwise_fit_on_device_matches_oracle(axis, with_sal, path, monkeypatch
     assert np.abs(m.predict(Y) - oc.em_predict(ref, Y128)).max() < 1e-8
 
 
+@pytest.mark.parametrize('D', [2, 3, 4, 5, 6, 7, 8])
+def test_shared_weight_kernel_every_sensor_count_translation_unit(D, monkeypatch):
+    """The cooperative shared-weight kernel is compiled in one translation unit per sensor count:
+    each is reached at the smallest shape with one full wave of frames plus a partial one
+    (tolerances of test_stepwise_fit_on_device_matches_oracle)."""
+    from oracle import cacgmm as oc, synth
+    from pb_bss_amd import engine
+    from pb_bss_amd.distribution import CACGMMTrainer
+    Y, init = synth.make_stft(3, 70, D, 2, seed=D)
+    Y128 = Y.astype(np.complex128)
+    ref = _oracle_stepwise(Y128, init, 2, (-3, -1))
+    calls = []
+    real = engine.em_fit_shared
+    monkeypatch.setattr(engine, 'em_fit_shared', lambda *a, **k: calls.append(1) or real(*a, **k))
+    m = CACGMMTrainer().fit(Y, initialization=init, iterations=2, weight_constant_axis=(-3, -1))
+    assert calls  # the cooperative kernel really served the call
+    assert np.abs(m.weight - ref['weight']).max() < 1e-10
+    assert np.abs(m.predict(Y) - oc.em_predict(ref, Y128)).max() < 1e-8
+
+
 @pytest.mark.parametrize('axis', [(-3,), (-3, -1)])
 def test_shared_weight_fit_batched_model_init_and_fit_predict(axis):
     """Cooperative kernel with two utterances in one call (two weight groups), resumed from a

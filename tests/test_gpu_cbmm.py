@@ -115,7 +115,9 @@ def compare_model(model, ref, tol_w=1e-9, tol_b=1e-8):
                                            (3, 3, np.complex64, False),
                                            (4, 2, np.complex128, True),
                                            (6, 3, np.complex128, False),
-                                           (8, 4, np.complex128, False)])
+                                           (8, 4, np.complex128, False),
+                                           (5, 2, np.complex64, False),
+                                           (7, 2, np.complex128, False)])
 def test_trainer_vs_oracle(D, K, dtype, sal):
     from pb_bss_amd.distribution import CBMMTrainer
     y, init = mixture(4, 150, D, K, seed=D * 7 + K)

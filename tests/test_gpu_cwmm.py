@@ -64,6 +64,19 @@ def test_cwmm_config4_shape_and_mvdr():
     assert np.abs(w - w_ref).max() < 1e-6 * np.abs(w_ref).max()
 
 
+@pytest.mark.parametrize('D', [2, 3, 4, 5, 6, 7, 8])
+def test_cwmm_every_sensor_count_translation_unit(D):
+    """One translation unit per sensor count: each is reached at the smallest shape with one full
+    wave of frames plus a partial one (tolerance of test_cwmm_config4_shape_and_mvdr)."""
+    from pb_bss_amd.distribution import CWMMTrainer
+    from oracle import cwmm as ow, synth
+    Y, init = synth.make_stft(3, 70, D, 2, seed=D)
+    Y128 = Y.astype(np.complex128)
+    masks = CWMMTrainer().fit_predict(Y, initialization=init, iterations=2)
+    ref = ow.cwmm_predict(ow.cwmm_fit(Y128, init, iterations=2), Y128)
+    assert np.abs(masks - ref).max() < 1e-7
+
+
 def test_watson_trainer_and_scalar_functions():
     from pb_bss_amd.distribution import ComplexWatsonTrainer, CWMMTrainer
     from oracle import cwmm as ow

@@ -56,6 +56,19 @@ def test_single_m_step_and_predict(F, T, D, K):
     assert np.abs(_host(r['affiliation']) - mask).max() < 1e-9
 
 
+@pytest.mark.parametrize('D', [2, 3, 4, 5, 6, 7, 8])
+def test_every_sensor_count_translation_unit(D):
+    """One translation unit per sensor count: each is reached at the smallest shape with one full
+    wave of frames plus a partial one (tolerances of test_trajectory_small)."""
+    from oracle import synth
+    Y, init = synth.make_stft(3, 70, D, 2, seed=D)
+    m, mask = _oracle_fit(Y, init, 2)
+    r = _device_fit(Y, init, 2)
+    assert (_host(r['status']) & 3 == 0).all()
+    assert np.abs(_host(r['affiliation']) - mask).max() < 1e-7
+    assert np.abs(_host(r['weight'])[..., None] - m['weight']).max() < 1e-8
+
+
 @pytest.mark.parametrize('iters', [2, 5, 20])
 def test_trajectory_small(iters):
     from oracle import synth

@@ -611,3 +611,20 @@ def test_joint_models_frame_counts_around_the_chunk_size(T):
         got = trainer.fit_predict(Y, e, initialization=init, iterations=5, saliency=sal, **kw)
         ref = oe.joint_fit(kind, Y128, e64, init, 5, saliency=sal, **kw)
         assert np.abs(got - oe.joint_model_predict(ref, Y128, e64)).max() < 1e-6, (T, kind, kw)
+
+
+@pytest.mark.parametrize('D', [2, 3, 4, 5, 6, 7, 8])
+def test_joint_models_every_sensor_count_translation_unit(D):
+    """The spatial kernels of the joint models are compiled in one translation unit per sensor
+    count: each is reached by the rotated two-kernel loop (spherical Gaussian) and by the
+    three-kernel path (diagonal Gaussian) at the smallest shape with one full wave of frames plus
+    a partial one (tolerance of test_joint_models_frame_counts_around_the_chunk_size)."""
+    from pb_bss_amd.distribution import GCACGMMTrainer
+    from oracle import embed as oe, synth
+    F, T, K, E = 3, 70, 2, 12
+    Y, e, init = synth.make_joint(F, T, D, K, E, seed=D)
+    Y128, e64 = Y.astype(np.complex128), e.astype(np.float64)
+    for kw in ({}, dict(covariance_type='diagonal')):
+        got = GCACGMMTrainer().fit_predict(Y, e, initialization=init, iterations=2, **kw)
+        ref = oe.joint_fit('gaussian', Y128, e64, init, 2, **kw)
+        assert np.abs(got - oe.joint_model_predict(ref, Y128, e64)).max() < 1e-6, (D, kw)

@@ -1,4 +1,6 @@
 """CPU: host-side logic of the drop-in layer that needs no GPU."""
+import os
+
 import numpy as np
 import pytest
 
@@ -587,3 +589,57 @@ def test_bench_line_of_a_multi_rank_run_carries_the_strong_curve():
     assert d['config3']['mapping_identical_across_shardings'] is True
     assert d['verify']['gathered_masks_identical_on_all_ranks'] is True
 
+
+
+def _host_compiler():
+    import shutil
+    for cxx in (os.environ.get('CXX'), 'c++', 'g++', 'clang++', '/opt/rocm/llvm/bin/clang++'):
+        if cxx and shutil.which(cxx):
+            return shutil.which(cxx)
+    return None
+
+
+def test_dispatch_helpers_reach_every_case(tmp_path):
+    """csrc/dispatch.hpp turns a runtime value into a template argument for every launch site: each
+    value of a range reaches the lambda with its constant, values outside return
+    PBBSS_ERR_UNSUPPORTED without a call, the lambda's status is passed through.  Host-only C++17
+    (tests/cpp/dispatch_check.cpp), built with the host compiler: the header includes no HIP."""
+    import subprocess
+    cxx = _host_compiler()
+    if cxx is None:
+        pytest.skip('no host C++ compiler')
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / 'dispatch_check'
+    subprocess.run([cxx, '-std=c++17', '-Wall', '-Wextra', '-Werror', '-O1',
+                    '-I', os.path.join(root, 'pb_bss_amd', 'csrc'), '-I', os.path.join(root, 'include'),
+                    os.path.join(root, 'tests', 'cpp', 'dispatch_check.cpp'), '-o', str(exe)],
+                   check=True, capture_output=True, text=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+
+
+def test_dynamic_lds_attribute_is_set_in_one_function():
+    """hipFuncAttributeMaxDynamicSharedMemorySize belongs to a function on a device, shared by all
+    host threads: it may only be raised.  raise_lds_attribute (csrc/launch_util.hpp) keeps that
+    invariant; no launch site sets the attribute itself."""
+    import glob
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    token = 'hipFuncAttributeMaxDynamicSharedMemorySize'
+    users = {}
+    for path in sorted(glob.glob(os.path.join(root, 'pb_bss_amd', 'csrc', '*.h*'))):
+        with open(path) as f:
+            text = f.read()
+        if token in text:
+            users[os.path.basename(path)] = text
+    assert list(users) == ['launch_util.hpp'], list(users)
+    text = users['launch_util.hpp']
+    start = text.index('inline bool raise_lds_attribute(const void* fn')
+    depth, end = 0, None
+    for i in range(text.index('{', start), len(text)):
+        depth += {'{': 1, '}': -1}.get(text[i], 0)
+        if depth == 0:
+            end = i
+            break
+    assert end is not None
+    assert token not in text[:start] and token not in text[end:]
+    assert text[start:end].count('hipFuncSetAttribute(fn,') == text.count('hipFuncSetAttribute(fn,') > 0
