@@ -1,6 +1,7 @@
-// pbbss_joint_fit: the joint spatial+spectral models (N3).  The one entry point of the C-ABI
-// layer that talks to the communicator, the side stream, the exchange buffer and four kernel
-// families at once; a multi-kernel loop enqueued asynchronously on `stream` (no host sync).
+// extern "C" boundary of the joint spatial+spectral models (include/pbbss.h, N3): pbbss_joint_fit.
+// The one entry point of the C-ABI layer that talks to the communicator, the side stream, the
+// exchange buffer and four kernel families at once; a multi-kernel loop enqueued asynchronously on
+// `stream` (no host sync).  No device code lives here.
 #include "handle.hpp"
 #include <cstdlib>
 #include "gauss_full.hpp"
@@ -238,24 +239,29 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
                                   h->cfg.lds_limit, s);
   };
   auto gen_e_step = [&](double* aff_out, double eps, bool for_m_step, int inline_pa) -> int {
+    pbbss::GenEstepArgs e{g_yt, o->obs_is_c128, PBBSS_LAYOUT_DT, F, T, D, K,
+                          static_cast<const double*>(out_eigvec), out_eigval, out_weight, wb, wk,
+                          wt};
+    e.raw_dt = 1;
     if (inline_pa) {
       // spatial log-pdf and quadratic forms first, then the per-bin permutation search
-      int r = pbbss::launch_gen_estep(g_yt, o->obs_is_c128, PBBSS_LAYOUT_DT, F, T, D, K,
-                                      static_cast<const double*>(out_eigvec), out_eigval, out_weight,
-                                      wb, wk, wt, nullptr, 0.0, nullptr, g_q, g_lp, s, g_state,
-                                      nullptr, nullptr, nullptr, /*raw_dt=*/1);
+      e.out_q = g_q;
+      e.out_logpdf = g_lp;
+      int r = pbbss::launch_gen_estep(e, g_state, s);
       if (r != PBBSS_OK) return r;
       return pbbss::launch_gen_joint_pa(g_yt, o->obs_is_c128, F, T, D, K, g_lp, g_q, slp,
                                         o->spatial_weight, out_weight, wb, wk, wt, saliency, eps,
                                         aff_out, for_m_step ? g_mw : nullptr,
                                         for_m_step ? g_zero : nullptr, s);
     }
-    return pbbss::launch_gen_estep(g_yt, o->obs_is_c128, PBBSS_LAYOUT_DT, F, T, D, K,
-                                   static_cast<const double*>(out_eigvec), out_eigval, out_weight,
-                                   wb, wk, wt, nullptr, eps, aff_out, nullptr, nullptr, s, g_state,
-                                   saliency, for_m_step ? g_mw : nullptr,
-                                   for_m_step ? g_zero : nullptr, /*raw_dt=*/1, slp,
-                                   o->spatial_weight);
+    e.eps = eps;
+    e.out_aff = aff_out;
+    e.saliency = saliency;
+    e.out_mweight = for_m_step ? g_mw : nullptr;
+    e.out_zero = for_m_step ? g_zero : nullptr;
+    e.extra = slp;
+    e.spatial_scale = o->spatial_weight;
+    return pbbss::launch_gen_estep(e, g_state, s);
   };
   if (gen) {
     if ((rc = pbbss::launch_gen_transpose(observation, o->obs_is_c128, F, T, D, g_yt, s)) != PBBSS_OK)
@@ -371,25 +377,26 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
       const bool side = side_allowed && !reduce && h->cfg.side_stream && !fin_in_launch;
       hipStream_t fs = s;
       if (side) {
-        if (hipEventRecord(h->cfg.ev_fork, s) != hipSuccess ||
-            hipStreamWaitEvent(h->cfg.side_stream, h->cfg.ev_fork, 0) != hipSuccess)
-          return PBBSS_ERR_HIP;
+        if ((rc = pbbss::side_fork(h->cfg, s)) != PBBSS_OK) return rc;
         fs = h->cfg.side_stream;
       }
+      // The finalize goes onto the side stream BEFORE the spatial kernel is enqueued and the
+      // caller's stream waits for it only after the class weights, so with_side_stream's order
+      // does not fit: the two halves of the join, under its error policy -- once forked, the
+      // join is issued whatever fails in between, and the first error is returned.
       if (!fin_in_launch) {
         rc = pbbss::launch_joint_sweep_finalize(o->kind, embedding, o->embedding_is_f64, N, E, K,
                                                 o->min_concentration, o->max_concentration, part,
                                                 out_mean, out_scale, offset, prec, fs, reduce);
-        if (rc != PBBSS_OK) return rc;
       }
-      if (side && hipEventRecord(h->cfg.ev_join, fs) != hipSuccess) return PBBSS_ERR_HIP;
-      if ((rc = spatial_ms(it == o->iterations - 1 ? 2 : 1)) != PBBSS_OK) return rc;
-      if (o->weight_mode != PBBSS_JOINT_WEIGHT_FK) {
+      int rc_join = side ? pbbss::side_join_record(h->cfg) : PBBSS_OK;
+      if (rc == PBBSS_OK) rc = spatial_ms(it == o->iterations - 1 ? 2 : 1);
+      if (rc == PBBSS_OK && o->weight_mode != PBBSS_JOINT_WEIGHT_FK) {
         rc = pbbss::launch_joint_weight(o->weight_mode, aff, saliency, F, K, T, tmp, out_weight, s,
                                         reduce);
-        if (rc != PBBSS_OK) return rc;
       }
-      if (side && hipStreamWaitEvent(s, h->cfg.ev_join, 0) != hipSuccess) return PBBSS_ERR_HIP;
+      if (side && rc_join == PBBSS_OK) rc_join = pbbss::side_join_wait(h->cfg, s);
+      if (rc != PBBSS_OK || rc_join != PBBSS_OK) return rc != PBBSS_OK ? rc : rc_join;
       continue;
     } else {
       if ((rc = spectral()) != PBBSS_OK) return rc;

@@ -50,23 +50,24 @@ static int cw_launch_wide(const WatsonArgs& wa, const EmLaunchCfg& cfg, hipStrea
   return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
 }
 
-// Remainder problems [b_first, b_first + p.r) as split groups on the side stream, concurrent with
-// the main launch (em_inst.hip: launch_split; same exchange buffer, counters and epoch protocol).
+// Remainder problems [b_first, b_first + p.r) as split groups on `side`, concurrent with the main
+// launch (em_inst.hip: launch_split; same exchange buffer, counters and epoch protocol).
+template <int D, int K, typename YS>
+static int cw_prepare_split(const SplitPlan& p) {
+  const size_t lds = WatsonSplit<D, K, YS>::lds_bytes(p.window);
+  return raise_lds_attribute(cwmm_em_split_kernel<D, K, YS>, lds) ? PBBSS_OK : PBBSS_ERR_HIP;
+}
 template <int D, int K, typename YS>
 static int cw_launch_split(WatsonArgs wa, int64_t b_first, const SplitPlan& p,
-                           const EmLaunchCfg& cfg) {
+                           const EmLaunchCfg& cfg, hipStream_t side) {
   EmArgs& a = wa.em;
   const size_t lds = WatsonSplit<D, K, YS>::lds_bytes(p.window);
   auto kfn = cwmm_em_split_kernel<D, K, YS>;
-  if (!raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
-  if (hipStreamWaitEvent(cfg.side_stream, cfg.ev_fork, 0) != hipSuccess) return PBBSS_ERR_HIP;
   stamp_split(a, cfg, p, b_first, cfg.split_prio);
   a.spin_limit = cfg.spin_limit;
   a.xbuf_given = (unsigned)cfg.xbuf_bytes;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)(p.r * p.G)), dim3(kEmThreads), lds, cfg.side_stream, wa);
-  if (hipGetLastError() != hipSuccess) return PBBSS_ERR_HIP;
-  if (hipEventRecord(cfg.ev_join, cfg.side_stream) != hipSuccess) return PBBSS_ERR_HIP;
-  return PBBSS_OK;
+  hipLaunchKernelGGL(kfn, dim3((unsigned)(p.r * p.G)), dim3(kEmThreads), lds, side, wa);
+  return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
 }
 
 // weight_constant_axis (-3, -1): one cooperative launch per batch of groups whose workgroups fit
@@ -134,14 +135,14 @@ static int cw_launch_one(const WatsonArgs& wa, const EmLaunchCfg& cfg, hipStream
   }
   WatsonArgs main_wa = wa;
   main_wa.em.B = a.B - p.r;
-  if (hipEventRecord(cfg.ev_fork, stream) != hipSuccess) return PBBSS_ERR_HIP;
-  int rc = cw_launch_wide<D, K, YS>(main_wa, cfg, stream);
-  if (rc == PBBSS_ERR_UNSUPPORTED) rc = cw_launch_variant<D, K, YS, false>(main_wa, cfg, stream);
-  if (rc != PBBSS_OK) return rc;
-  rc = cw_launch_split<D, K, YS>(wa, a.B - p.r, p, cfg);
-  if (rc != PBBSS_OK) return rc;
-  if (hipStreamWaitEvent(stream, cfg.ev_join, 0) != hipSuccess) return PBBSS_ERR_HIP;
-  return PBBSS_OK;
+  return with_side_stream(
+      cfg, stream,
+      [&] {
+        int rc = cw_launch_wide<D, K, YS>(main_wa, cfg, stream);
+        if (rc == PBBSS_ERR_UNSUPPORTED) rc = cw_launch_variant<D, K, YS, false>(main_wa, cfg, stream);
+        return rc != PBBSS_OK ? rc : cw_prepare_split<D, K, YS>(p);
+      },
+      [&](hipStream_t side) { return cw_launch_split<D, K, YS>(wa, a.B - p.r, p, cfg, side); });
 }
 
 template <int D>

@@ -36,22 +36,23 @@ static int launch_variant(EmArgs a, const EmLaunchCfg& cfg, hipStream_t stream) 
   return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
 }
 
-// Remainder problems [b_first, b_first + p.r) as split groups on the side stream,
-// concurrent with the main launch (fork/join through events).
+// Remainder problems [b_first, b_first + p.r) as split groups on `side`, concurrent with the main
+// launch (with_side_stream).  prepare_split: the host half that does not touch the side stream.
 template <int D, int K, typename YS>
-static int launch_split(EmArgs a, int64_t b_first, const SplitPlan& p, const EmLaunchCfg& cfg) {
+static int prepare_split(const SplitPlan& p) {
+  const size_t lds = EmKernel<D, K, YS, false>::lds_bytes(p.window);
+  return raise_lds_attribute(cacgmm_em_split_kernel<D, K, YS>, lds) ? PBBSS_OK : PBBSS_ERR_HIP;
+}
+template <int D, int K, typename YS>
+static int launch_split(EmArgs a, int64_t b_first, const SplitPlan& p, const EmLaunchCfg& cfg,
+                        hipStream_t side) {
   const size_t lds = EmKernel<D, K, YS, false>::lds_bytes(p.window);
   auto kfn = cacgmm_em_split_kernel<D, K, YS>;
-  if (!raise_lds_attribute(kfn, lds)) return PBBSS_ERR_HIP;
-  // fork: everything enqueued on `stream` before the event (the inputs) precedes the side stream
-  if (hipStreamWaitEvent(cfg.side_stream, cfg.ev_fork, 0) != hipSuccess) return PBBSS_ERR_HIP;
   stamp_split(a, cfg, p, b_first, cfg.split_prio);
   a.spin_limit = cfg.spin_limit;
   a.xbuf_given = (unsigned)cfg.xbuf_bytes;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)(p.r * p.G)), dim3(kEmThreads), lds, cfg.side_stream, a);
-  if (hipGetLastError() != hipSuccess) return PBBSS_ERR_HIP;
-  if (hipEventRecord(cfg.ev_join, cfg.side_stream) != hipSuccess) return PBBSS_ERR_HIP;
-  return PBBSS_OK;
+  hipLaunchKernelGGL(kfn, dim3((unsigned)(p.r * p.G)), dim3(kEmThreads), lds, side, a);
+  return hipGetLastError() == hipSuccess ? PBBSS_OK : PBBSS_ERR_HIP;
 }
 
 template <int D, int K, typename YS>
@@ -65,18 +66,16 @@ static int launch_one(const EmArgs& a, const EmLaunchCfg& cfg, hipStream_t strea
   if (!p.ok) return launch_variant<D, K, YS, false>(a, cfg, stream);
   EmArgs main_a = a;
   main_a.B = a.B - p.r;
-  // The main launch goes out FIRST: the side-stream preparation of the split groups (fork wait,
-  // launch, join record) is a handful of host calls during which the device would otherwise idle;
-  // the members are independent of the main workgroups and finish long before them.
-  // (hipExtAnyOrderLaunch -- the split kernel as a barrier-less packet of the SAME queue -- would
-  // need neither stream nor events, but is documented as unsupported on gfx9.)
-  if (hipEventRecord(cfg.ev_fork, stream) != hipSuccess) return PBBSS_ERR_HIP;
-  int rc = launch_variant<D, K, YS, false>(main_a, cfg, stream);
-  if (rc != PBBSS_OK) return rc;
-  rc = launch_split<D, K, YS>(a, a.B - p.r, p, cfg);
-  if (rc != PBBSS_OK) return rc;
-  if (hipStreamWaitEvent(stream, cfg.ev_join, 0) != hipSuccess) return PBBSS_ERR_HIP;
-  return PBBSS_OK;
+  // The main launch goes out first (with_side_stream); the members are independent of the main
+  // workgroups.  (hipExtAnyOrderLaunch -- the split kernel as a barrier-less packet of the SAME
+  // queue -- would need neither stream nor events, but is documented as unsupported on gfx9.)
+  return with_side_stream(
+      cfg, stream,
+      [&] {
+        const int rc = launch_variant<D, K, YS, false>(main_a, cfg, stream);
+        return rc != PBBSS_OK ? rc : prepare_split<D, K, YS>(p);
+      },
+      [&](hipStream_t side) { return launch_split<D, K, YS>(a, a.B - p.r, p, cfg, side); });
 }
 
 template <int D>

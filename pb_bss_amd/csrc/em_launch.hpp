@@ -15,30 +15,6 @@ namespace pbbss {
 // the step-wise loop -- run without them (inline aligner loop 387 -> 376 us per iteration).
 constexpr int kSplitMinIterations = 3;
 
-struct EmLaunchCfg {
-  int num_cu;        // compute units of the bound device
-  size_t lds_limit;  // usable LDS bytes per workgroup
-  // grow-only device scratch owned by the handle (frame arrays of long utterances)
-  void* (*get_scratch)(void* ctx, size_t bytes);
-  void* scratch_ctx;
-  // split-bin remainder launches: side stream + fork/join events + exchange buffer
-  hipStream_t side_stream;
-  hipEvent_t ev_fork, ev_join;
-  char* xbuf;        // [xbuf_bytes] device memory: counters, error word, slabs
-  size_t xbuf_bytes;
-  int allow_split;   // 0 disables the split variant (tests / debugging)
-  int split_window;  // frames per workgroup of a split problem (multiple of 64)
-  int split_prio;    // s_setprio level of the split waves (float64 kernels)
-  int split_prio32;  // ... of the packed-FP32 kernel's member workgroups
-  int* split_epoch;  // host counter stamping the launches of the split protocol
-  unsigned spin_limit;  // EmArgs::spin_limit of every launch (0: the kernels' defaults)
-  // kernel timing (pbbss_set_timing): start / stop events attached to the DISPATCH of the EM kernel
-  // itself (hipExtLaunchKernelGGL: timestamps of the kernel's own completion signal) instead of
-  // two hipEventRecord packets around the call -- those cost ~30 us of queue time per step
-  // (tools/launch_gap.py).  Null: timing off.
-  hipEvent_t ev_t0, ev_t1;
-};
-
 // launch stamp of the split protocol: never 0 (= "launcher clears the word") nor 1 (what the
 // cooperative shared-weight kernel writes)
 inline int next_split_epoch(const EmLaunchCfg& cfg) {

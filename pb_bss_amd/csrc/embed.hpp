@@ -13,7 +13,7 @@ constexpr int kEmbedMaxE = 256;   // embedding dimension (one workgroup row of t
 
 // Sharded fits (the points of ONE mixture spread over several GPUs): called between the kernel
 // that writes per-chunk partial sums and the kernel that finalises them, to sum the partials over
-// the ranks in place (capi.hip binds it to an ncclAllReduce on the launch stream).
+// the ranks in place (capi_joint.hip binds it to an ncclAllReduce on the launch stream).
 struct PartialReduce {
   int (*fn)(void* ctx, double* buf, size_t count, hipStream_t s);
   void* ctx;
@@ -164,5 +164,41 @@ int launch_mixture_weight(const double* aff, const double* sal, int64_t Bo, int6
 int launch_log_pdf_to_affiliation(const double* lp, int64_t B, int K, int64_t N, const double* w,
                                   int64_t wb, int64_t wk, int64_t wn, const uint8_t* act,
                                   double eps, double* out, hipStream_t s);
+
+
+// ---- embed_fit.hip (host code only): the EM loop of the two real-embedding mixtures,
+// pbbss_vmfmm_fit (kind = PBBSS_EMBED_VMF, rows unit-normalised first, vmfmm.py:76-78) and
+// pbbss_gmm_fit (PBBSS_EMBED_GAUSS_SPHERICAL, gmm.py:126-171, covariance_type 'spherical').
+struct EmbedMixtureFit {
+  int kind;
+  const void* y;  // (B,N,E)
+  int y_is_f64;
+  int64_t B, N;
+  int E, K;
+  const double* gamma0;  // (B,K,N) or null: start from the model (iterations == 0)
+  const double *in_mean, *in_scale, *in_weight, *saliency;
+  const double* fixed_scale;  // fixed_covariance (B,K) or null
+  int iterations, weight_mode, final_predict;
+  double min_concentration, max_concentration;
+  double *out_mean, *out_scale, *out_weight;
+  double *out_affiliation, *out_log_pdf;  // or null
+};
+// The loop runs on one of four paths; embed_mixture_path is the one place that chooses.
+enum class EmbedFitPath {
+  kWide,       // 9 ... 64 classes: one fused sweep per iteration on class tiles (embed_wide.hip)
+  kPerBin,     // many small vMF mixtures: the whole loop in ONE launch, a workgroup per mixture
+  kFused,      // vMF: ONE pass over the embedding per iteration (vmf_em_kernel)
+  kTwoKernel,  // transposed copy for the E-step, row-major sweep for the M-step
+};
+EmbedFitPath embed_mixture_path(const EmbedMixtureFit& f, size_t lds_limit);
+// what the path needs of the work area; an array the path does not use stays null
+struct EmbedMixtureWork {
+  double* wide;           // kWide: embed_wide_work_doubles()
+  double *yd, *rowscale;  // (B,E,N) transposed copy, INPUT type; (B,N) vMF: 1 / |y_n|
+  double *aff, *part;     // (B,K,N); embed_partial_doubles() / vmf_fused_partial_doubles()
+  double *offset, *prec;  // (B,K)
+};
+int run_embed_mixture_fit(EmbedFitPath path, const EmbedMixtureFit& f, const EmbedMixtureWork& w,
+                          size_t lds_limit, int num_cu, hipStream_t s);
 
 }  // namespace pbbss

@@ -18,7 +18,7 @@ constexpr int kEmbedWideMaxK = 64;  // four class tiles of 16
 // moment sets, the padded sweep model, per-class weight sums, the common shift)
 size_t embed_wide_work_doubles(int64_t B, int64_t N, int E, int K);
 
-// The EM loop of pbbss_vmfmm_fit / pbbss_gmm_fit (embed_mixture_fit in capi.hip) for K > 8: per
+// The EM loop of pbbss_vmfmm_fit / pbbss_gmm_fit (run_embed_mixture_fit in embed_fit.hip) for K > 8: per
 // iteration ONE sweep over the caller's row-major y (wide_sweep_kernel: E-step tile, softmax
 // across the DPP row, M-step tiles from the same LDS rows) + the ordered finalize + the model
 // kernel that prepares the next sweep.  Arguments as embed_mixture_fit; fixed_scale (B, K) or

@@ -720,4 +720,44 @@ int launch_gauss_full_logpdf(const void* y, int y_is_f64, int64_t B, int64_t N, 
   });
 }
 
+
+int run_gmm_full_fit(const GmmFullFit& f, const GmmFullWork& w, hipStream_t s) {
+  const int64_t B = f.B, N = f.N;
+  const int E = f.E, K = f.K, f64 = f.y_is_f64;
+  const size_t nm = (size_t)B * K * E * E;
+  int rc;
+  if (!f.gamma0) {  // start from the model
+    rc = copy_model({f.out_mean, f.in_mean, (size_t)B * K * E * 8},
+                    {f.out_covariance, f.in_covariance, nm * 8},
+                    {f.out_weight, f.in_weight, (size_t)B * K * 8}, s);
+    if (rc != PBBSS_OK) return rc;
+    rc = launch_gauss_full_factor(f.out_covariance, B * K, E, w.mq, w.off, f.out_status, s);
+    if (rc != PBBSS_OK) return rc;
+  }
+  for (int it = 0; it < f.iterations; ++it) {
+    const double* src = f.gamma0;
+    if (it > 0) {  // gmm.py:129-130
+      rc = launch_gauss_full_logpdf(f.y, f64, B, N, E, K, f.out_mean, w.mq, w.off, f.out_weight,
+                                    nullptr, w.aff, s);
+      if (rc != PBBSS_OK) return rc;
+      src = w.aff;
+    }
+    rc = launch_gauss_full_fit(f.y, f64, B, N, E, K, src, f.saliency, w.part, f.out_mean,
+                               f.out_covariance, f.fixed_covariance ? nullptr : w.mq,
+                               f.fixed_covariance ? nullptr : w.off, w.s0, f.out_status, s);
+    if (rc != PBBSS_OK) return rc;
+    rc = launch_gauss_full_weights(w.s0, B, K, f.weight_mode, f.out_weight, s);
+    if (rc != PBBSS_OK) return rc;
+    if (f.fixed_covariance) {  // gmm.py:160-167
+      if ((rc = copy_d2d(f.out_covariance, f.fixed_covariance, nm * 8, s)) != PBBSS_OK) return rc;
+      rc = launch_gauss_full_factor(f.out_covariance, B * K, E, w.mq, w.off, f.out_status, s);
+      if (rc != PBBSS_OK) return rc;
+    }
+  }
+  if (f.final_predict && (f.out_affiliation || f.out_log_pdf))
+    return launch_gauss_full_logpdf(f.y, f64, B, N, E, K, f.out_mean, w.mq, w.off, f.out_weight,
+                                    f.out_log_pdf, f.out_affiliation, s);
+  return PBBSS_OK;
+}
+
 }  // namespace pbbss

@@ -36,4 +36,26 @@ int launch_gauss_full_factor(const double* cov, int64_t BK, int E, double* out_m
 int launch_gauss_full_logpdf(const void* y, int y_is_f64, int64_t B, int64_t N, int E, int K,
                              const double* mean, const double* mq, const double* offset,
                              const double* weight, double* out_lp, double* out_aff, hipStream_t s);
+
+// The EM loop of pbbss_gmm_full_fit (gmm.py:126-171, covariance_type 'full'), enqueued back to
+// back; the model lives in the caller's output arrays.
+struct GmmFullFit {
+  const void* y;  // (B,N,E)
+  int y_is_f64;
+  int64_t B, N;
+  int E, K;
+  const double* gamma0;  // (B,K,N) or null: start from the model (iterations == 0)
+  const double *in_mean, *in_covariance, *in_weight, *saliency;
+  const double* fixed_covariance;  // (B,K,E,E) or null
+  int iterations, weight_mode, final_predict;
+  double *out_mean, *out_covariance, *out_weight;
+  double *out_affiliation, *out_log_pdf;  // or null
+  int32_t* out_status;
+};
+struct GmmFullWork {
+  double* part;      // gauss_full_partial_doubles()
+  double *mq, *aff;  // (B,K,E,E); (B,K,N)
+  double *off, *s0;  // (B,K)
+};
+int run_gmm_full_fit(const GmmFullFit& f, const GmmFullWork& w, hipStream_t s);
 }  // namespace pbbss

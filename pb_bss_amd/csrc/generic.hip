@@ -1152,20 +1152,18 @@ int set_lds(KFN kfn, size_t lds, size_t lds_limit) {
 bool gen_supported(int D, int K) { return D >= 2 && D <= kGenMaxD && K >= 1 && K <= kGenMaxK; }
 bool gen_em_supported(int D, int K) { return D >= 2 && D <= kGenMaxDEm && K >= 1 && K <= kGenMaxK; }
 
-int launch_gen_estep(const void* y, int y_is_c128, int layout, int64_t B, int T, int D, int K,
-                     const double* eigvec, const double* eigval, const double* weight, int64_t wb,
-                     int64_t wk, int64_t wt, const uint8_t* activity, double eps, double* out_aff,
-                     double* out_q, double* out_logpdf, hipStream_t s,
-                     const GenInverseState& state, const double* saliency, double* out_mweight,
-                     int32_t* out_zero, int raw_dt, const double* extra, double spatial_scale) {
+int launch_gen_estep(const GenEstepArgs& e, const GenInverseState& state, hipStream_t s) {
+  const int64_t B = e.B;
+  const int T = e.T, D = e.D, K = e.K, y_is_c128 = e.y_is_c128;
   if (!gen_em_supported(D, K)) return PBBSS_ERR_UNSUPPORTED;
   if (!state.inv || !state.logdet) return PBBSS_ERR_INVALID_ARG;
   const int DP = gen_state_ld(D);
-  GenEigToInv c{eigvec, eigval, D, DP, state.ok, state.inv, state.logdet};
+  GenEigToInv c{e.eigvec, e.eigval, D, DP, state.ok, state.inv, state.logdet};
   hipLaunchKernelGGL(gen_eig_to_inv_kernel, dim3((unsigned)(B * K)), dim3(kGenThreads), 0, s, c);
-  GenEstep a{y, layout, B, T, D, K, state.inv, state.logdet, weight, wb, wk, wt, activity, eps,
-             out_aff, out_q, out_logpdf, saliency, out_mweight, out_zero,
-             (layout == PBBSS_LAYOUT_TD || raw_dt) ? 1 : 0, extra, spatial_scale};
+  GenEstep a{e.y, e.layout, B, T, D, K, state.inv, state.logdet, e.weight, e.wb, e.wk, e.wt,
+             e.activity, e.eps, e.out_aff, e.out_q, e.out_logpdf, e.saliency, e.out_mweight,
+             e.out_zero, (e.layout == PBBSS_LAYOUT_TD || e.raw_dt) ? 1 : 0, e.extra,
+             e.spatial_scale};
   const dim3 grid((unsigned)B, (unsigned)((T + kGenThreads - 1) / kGenThreads));
   if (grid.y > 65535u) return PBBSS_ERR_UNSUPPORTED;
   const size_t lds = (size_t)2 * K * kGenThreads * sizeof(double);  // softmax slots [2][K][thread]
@@ -1502,6 +1500,129 @@ int launch_gen_inverse(const double* a, int64_t N, int D, double eig_floor, doub
     hipLaunchKernelGGL(gen_inv_kernel<36>, dim3((unsigned)N), dim3(kGenThreads), 0, s, g);
   }
   return ok_or_hip();
+}
+
+
+namespace {
+// One chain of launches for the bins [b0, b0 + nb) on `st`: every array is sliced along the bins
+// (nothing couples them under the per-bin weight modes of pbbss_cacgmm_fit).
+int gen_cacgmm_chain(const GenCacgmmFit& f, const GenCacgmmWork& w, size_t lds_limit, int64_t b0,
+                     int64_t nb, hipStream_t st) {
+  const int T = f.T, D = f.D, K = f.K;
+  const bool has_model = f.gamma0 == nullptr;
+  const size_t ysz = f.y_is_c128 ? 16 : 8;
+  const size_t ld2 = gen_state_doubles(1, D);
+  const size_t m0 = (size_t)b0 * K, nm = (size_t)nb * K;
+  const char* y_c = static_cast<const char*>(f.y) + (size_t)b0 * T * D * ysz;
+  const double* gamma0_c = f.gamma0 ? f.gamma0 + m0 * T : nullptr;
+  const double* sal_c = f.saliency ? f.saliency + (size_t)b0 * T : nullptr;
+  double* evec_c = static_cast<double*>(f.out_eigvec) + m0 * D * D * 2;
+  double* eval_c = f.out_eigval + m0 * D;
+  double* w_c = f.out_weight + m0;
+  int32_t* st_c = f.out_status + m0;
+  double* aff_c = w.aff + m0 * T;
+  double* mw_c = w.mw + m0 * T;
+  double* cov_c = w.cov + m0 * D * D * 2;
+  int32_t* zero_c = w.zero_bin + b0;
+  int32_t* ok_c = w.inv_ok + m0;
+  const GenInverseState state{w.inv + m0 * ld2, w.inv_logdet + m0, ok_c};
+  const GenInverseState state_from_eig{w.inv + m0 * ld2, w.inv_logdet + m0, nullptr};
+  int rc;
+  if (has_model) {
+    rc = copy_model({evec_c, static_cast<const double*>(f.in_eigvec) + m0 * D * D * 2, nm * D * D * 16},
+                    {eval_c, f.in_eigval + m0 * D, nm * D * 8}, {w_c, f.in_weight + m0, nm * 8}, st);
+    if (rc != PBBSS_OK) return rc;
+  }
+  if (hipMemsetAsync(st_c, 0, nm * sizeof(int32_t), st) != hipSuccess) return PBBSS_ERR_HIP;
+  // bins with an all-zero frame (flagged by the E-step / the initial weights) never take
+  // the inverse fast path
+  if (hipMemsetAsync(zero_c, 0, (size_t)nb * sizeof(int32_t), st) != hipSuccess) return PBBSS_ERR_HIP;
+  // E-steps read a (B, D, T) copy of the raw observation (lane = frame is then the contiguous
+  // axis); the covariance kernel keeps the caller's (B, T, D) array (its lanes span the channels)
+  GenEstepArgs e{};
+  e.y = y_c;
+  e.y_is_c128 = f.y_is_c128;
+  e.layout = PBBSS_LAYOUT_TD;
+  e.B = nb;
+  e.T = T;
+  e.D = D;
+  e.K = K;
+  e.eigvec = evec_c;
+  e.eigval = eval_c;
+  e.weight = w_c;
+  e.wb = K;
+  e.wk = 1;
+  e.wt = 0;
+  e.raw_dt = 1;
+  if (w.yt) {
+    char* yt_c = w.yt + (size_t)b0 * T * D * ysz;
+    if ((rc = launch_gen_transpose(y_c, f.y_is_c128, nb, T, D, yt_c, st)) != PBBSS_OK) return rc;
+    e.y = yt_c;
+    e.layout = PBBSS_LAYOUT_DT;
+  }
+  GenEstepArgs loop = e;  // the E-step of the loop also leaves the M-step weights
+  loop.activity = f.activity ? f.activity + m0 * T : nullptr;
+  loop.eps = f.affiliation_eps;
+  loop.out_aff = aff_c;
+  loop.saliency = sal_c;
+  loop.out_mweight = mw_c;
+  loop.out_zero = zero_c;
+  for (int it = 0; it < f.iterations; ++it) {
+    const double* g_src = gamma0_c;
+    if (it > 0 || has_model) {
+      // from the second iteration on, classes whose inverse was accepted skip (V, lambda)
+      if ((rc = launch_gen_estep(loop, it > 0 ? state : state_from_eig, st)) != PBBSS_OK) return rc;
+      g_src = aff_c;
+    } else {
+      rc = launch_gen_init_weights(e.y, f.y_is_c128, e.layout, nb, T, D, K, gamma0_c, sal_c, mw_c,
+                                   zero_c, st);
+      if (rc != PBBSS_OK) return rc;
+    }
+    rc = launch_gen_mstep_cov(y_c, f.y_is_c128, nb, T, D, K, mw_c, g_src, sal_c, f.weight_mode,
+                              w.csum + m0, cov_c, w_c, st);
+    if (rc != PBBSS_OK) return rc;
+    const bool last = it + 1 == f.iterations;
+    if (!last && !f.force_eig) {
+      rc = launch_gen_inverse(cov_c, (int64_t)nm, D, f.eigenvalue_floor, state.inv, state.logdet,
+                              ok_c, st, zero_c, K);
+      if (rc != PBBSS_OK) return rc;
+    } else if (!last) {
+      if (hipMemsetAsync(ok_c, 0, nm * sizeof(int32_t), st) != hipSuccess) return PBBSS_ERR_HIP;
+    }
+    // the eigendecomposition the caller sees comes from the last iteration; before that it
+    // only runs for the matrices the inverse test rejected.  Status words are those of the
+    // last iteration (earlier ones are overwritten).
+    rc = launch_gen_heev(cov_c, (int64_t)nm, D, f.covariance_norm, f.eigenvalue_floor, eval_c,
+                         evec_c, st_c, lds_limit, st, last ? nullptr : ok_c);
+    if (rc != PBBSS_OK) return rc;
+  }
+  if (f.final_predict && (f.out_affiliation || f.out_quadratic_form)) {
+    e.out_aff = f.out_affiliation ? f.out_affiliation + m0 * T : nullptr;
+    e.out_q = f.out_quadratic_form ? f.out_quadratic_form + m0 * T : nullptr;
+    return launch_gen_estep(e, state_from_eig, st);
+  }
+  return PBBSS_OK;
+}
+}  // namespace
+
+int run_gen_cacgmm_fit(const GenCacgmmFit& f, const GenCacgmmWork& w, const EmLaunchCfg& cfg,
+                       hipStream_t s) {
+  // 2^n + 1 bins (every standard STFT size): the last bin turns a whole number of residency
+  // rounds into that number plus one straggler in EVERY kernel of the loop (513 bins x 8
+  // E-step wavefronts = 4104 on 4096 slots; 513 x 6 covariance workgroups on 768 slots).  A few
+  // remainder bins therefore run as their own chain on the side stream, concurrently with the
+  // main chain -- forked once, joined once: the bins do not interact inside the loop.
+  const int64_t per_round = cfg.num_cu > 0 ? cfg.num_cu : 256;
+  const int64_t rem = f.B % per_round;
+  const bool peel = cfg.side_stream && cfg.allow_split && f.B > per_round && rem > 0 &&
+                    rem * 16 <= per_round;
+  if (!peel) return gen_cacgmm_chain(f, w, cfg.lds_limit, 0, f.B, s);
+  int rc = side_fork(cfg, s);
+  if (rc != PBBSS_OK) return rc;
+  rc = gen_cacgmm_chain(f, w, cfg.lds_limit, 0, f.B - rem, s);
+  const int rc_side = gen_cacgmm_chain(f, w, cfg.lds_limit, f.B - rem, rem, cfg.side_stream);
+  const int rc_join = side_join(cfg, s);
+  return rc != PBBSS_OK ? rc : rc_side != PBBSS_OK ? rc_side : rc_join;
 }
 
 }  // namespace pbbss

@@ -29,16 +29,26 @@ struct GenInverseState {
 };
 
 // a2-a4: posteriors / quadratic form / log-pdf from an eigen-parameterised model
-int launch_gen_estep(const void* y, int y_is_c128, int layout, int64_t B, int T, int D, int K,
-                     const double* eigvec, const double* eigval, const double* weight, int64_t wb,
-                     int64_t wk, int64_t wt, const uint8_t* activity, double eps, double* out_aff,
-                     double* out_q, double* out_logpdf, hipStream_t s,
-                     const GenInverseState& state, const double* saliency = nullptr,
-                     double* out_mweight = nullptr, int32_t* out_zero = nullptr,
-                     int raw_dt = 0,  // raw_dt: layout DT holds RAW values (transposed copy)
-                     // joint spatial + spectral models: posterior exponent = spatial_scale *
-                     // log-pdf + extra[b,k,t] (gcacgmm.py:66-117)
-                     const double* extra = nullptr, double spatial_scale = 1.0);
+struct GenEstepArgs {
+  const void* y;
+  int y_is_c128, layout;
+  int64_t B;
+  int T, D, K;
+  const double *eigvec, *eigval, *weight;  // weight read as weight[b * wb + k * wk + t * wt]
+  int64_t wb, wk, wt;
+  const uint8_t* activity = nullptr;
+  double eps = 0.0;
+  double *out_aff = nullptr, *out_q = nullptr, *out_logpdf = nullptr;
+  // EM loop: M-step weights and zero-frame flags of launch_gen_mstep_cov (see below)
+  const double* saliency = nullptr;
+  double* out_mweight = nullptr;
+  int32_t* out_zero = nullptr;
+  int raw_dt = 0;  // layout DT holds RAW values (transposed copy)
+  // joint spatial + spectral models: posterior exponent = spatial_scale * log-pdf + extra[b,k,t]
+  const double* extra = nullptr;  // (gcacgmm.py:66-117)
+  double spatial_scale = 1.0;
+};
+int launch_gen_estep(const GenEstepArgs& a, const GenInverseState& state, hipStream_t s);
 
 // Joint models with inline permutation alignment (mixture_model_utils.py:58-130): from the
 // spatial log-pdf / quadratic forms of launch_gen_estep (out_logpdf, out_q) and the spectral
@@ -100,6 +110,37 @@ int launch_gen_inverse(const double* a, int64_t N, int D, double eig_floor, doub
                        double* out_logdet, int32_t* out_ok, hipStream_t s,
                        const int32_t* veto = nullptr, int K = 1);
 
+// The EM loop of pbbss_cacgmm_fit at generic sizes: per iteration E-step, covariance + weights,
+// inverse / eigendecomposition, enqueued back to back; the model lives in the caller's output
+// buffers.  A few remainder bins of a 2^n + 1 bin batch run as their own chain on cfg.side_stream.
+struct EmLaunchCfg;
+struct GenCacgmmFit {
+  const void* y;  // (B, T, D)
+  int y_is_c128;
+  int64_t B;
+  int T, D, K;
+  const double* gamma0;  // (B,K,T) or null: start from the model (in_*)
+  const void* in_eigvec;
+  const double *in_eigval, *in_weight, *saliency;
+  const uint8_t* activity;
+  int iterations, covariance_norm, weight_mode, force_eig, final_predict;
+  double affiliation_eps, eigenvalue_floor;
+  void* out_eigvec;
+  double *out_eigval, *out_weight;
+  int32_t* out_status;
+  double *out_affiliation, *out_quadratic_form;  // or null
+};
+struct GenCacgmmWork {
+  double *aff, *mw;  // (B,K,T): posteriors; M-step weights gamma sal / q / |y|^2 of every frame
+  double* cov;       // c128 (B,K,D,D)
+  double *inv, *inv_logdet;     // gen_state_doubles(B K, D); (B,K)
+  int32_t *inv_ok, *zero_bin;   // (B,K); (B)
+  double* csum;                 // (B,K)
+  char* yt;  // (B, D, T) frame-contiguous copy for the E-steps, or null (B > 65535)
+};
+int run_gen_cacgmm_fit(const GenCacgmmFit& f, const GenCacgmmWork& w, const EmLaunchCfg& cfg,
+                       hipStream_t s);
+
 // ---- complex-Watson mixture at generic sizes (generic_watson.hip; cwmm.py, complex_watson.py)
 struct GenWatsonSpline {
   const double* t;  // knots (n_coef + 3), device
@@ -119,5 +160,32 @@ int launch_gen_watson_lognorm(const double* conc, int64_t N, int D, double* out,
 int launch_gen_watson_finish(const double* eigval, const double* eigvec, int64_t N, int D,
                              const GenWatsonSpline& sp, double* out_mode, double* out_conc,
                              double* out_lognorm, hipStream_t s);
+
+
+// The EM loop of pbbss_cwmm_fit at generic sizes: per iteration class log-pdfs -> softmax with the
+// weights -> masked covariance of the unit-norm frames + weights -> eigh -> principal pair,
+// concentration, ln c; enqueued back to back.  mode / conc / weight / status hold the model
+// (the caller's outputs, or work arrays where the caller passed none).
+struct GenWatsonFit {
+  const void* y;  // (B, T, D)
+  int y_is_c128;
+  int64_t B;
+  int T, D, K;
+  const double* gamma0;  // (B,K,T) or null: start from the model (in_*)
+  const void* in_mode;
+  const double *in_concentration, *in_weight, *saliency;
+  int iterations, weight_mode, final_predict;
+  GenWatsonSpline spline;
+  double *mode, *conc, *weight;
+  int32_t* status;
+  double *out_affiliation, *out_log_pdf;  // or null
+};
+struct GenWatsonWork {
+  double *aff, *lp;     // (B,K,T)
+  double *cov, *evec;   // c128 (B,K,D,D)
+  double *eval, *lognorm;  // (B,K,D); (B,K)
+};
+int run_gen_watson_fit(const GenWatsonFit& f, const GenWatsonWork& w, size_t lds_limit,
+                       hipStream_t s);
 
 }  // namespace pbbss

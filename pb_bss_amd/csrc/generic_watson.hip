@@ -5,9 +5,11 @@
 // The fused kernel of cwmm.hpp serves D <= 8, K <= 4; here an iteration is
 //   class log-pdfs (below) -> softmax with the weights (mixw.hip) -> gen_cov mode 3 (weights,
 //   masked covariance of the unit-norm frames) -> gen_heev -> principal pair, kappa, ln c (below)
-// enqueued back to back by pbbss_cwmm_fit.
+// enqueued back to back by run_gen_watson_fit (at the end of this file).
 #include "generic.hpp"
 #include <cmath>
+#include "embed.hpp"  // launch_log_pdf_to_affiliation
+#include "launch_util.hpp"
 #include "pbbss_dev.hpp"
 
 namespace pbbss {
@@ -146,6 +148,50 @@ int launch_gen_watson_finish(const double* eigval, const double* eigvec, int64_t
   hipLaunchKernelGGL(gen_watson_finish_kernel, dim3((unsigned)((N + kWT - 1) / kWT)), dim3(kWT), 0,
                      s, eigval, eigvec, N, D, sp, out_mode, out_conc, out_lognorm);
   return ok_or_hip_w();
+}
+
+
+int run_gen_watson_fit(const GenWatsonFit& f, const GenWatsonWork& w, size_t lds_limit,
+                       hipStream_t s) {
+  const int64_t B = f.B;
+  const int T = f.T, D = f.D, K = f.K;
+  const size_t nmat = (size_t)B * K;
+  const bool has_model = f.gamma0 == nullptr;
+  int rc;
+  if (hipMemsetAsync(f.status, 0, nmat * sizeof(int32_t), s) != hipSuccess) return PBBSS_ERR_HIP;
+  if (has_model) {
+    rc = copy_model({f.mode, f.in_mode, nmat * D * 16}, {f.conc, f.in_concentration, nmat * 8},
+                    {f.weight, f.in_weight, nmat * 8}, s);
+    if (rc != PBBSS_OK) return rc;
+    if ((rc = launch_gen_watson_lognorm(f.conc, (int64_t)nmat, D, w.lognorm, s)) != PBBSS_OK)
+      return rc;
+  }
+  auto e_step = [&](double* out_lp, double* out_aff) {
+    int r = launch_gen_watson_logpdf(f.y, f.y_is_c128, B, T, D, K, f.mode, f.conc, w.lognorm,
+                                     out_lp, s);
+    if (r != PBBSS_OK || !out_aff) return r;
+    return launch_log_pdf_to_affiliation(out_lp, B, K, T, f.weight, K, 1, 0, nullptr, 0.0, out_aff,
+                                         s);
+  };
+  for (int it = 0; it < f.iterations; ++it) {
+    const double* g_src = f.gamma0;
+    if (it > 0 || has_model) {
+      if ((rc = e_step(w.lp, w.aff)) != PBBSS_OK) return rc;
+      g_src = w.aff;
+    }
+    rc = launch_gen_cov(f.y, f.y_is_c128, PBBSS_LAYOUT_TD, B, T, D, K, g_src, (int64_t)K * T,
+                        nullptr, f.saliency, /*mode=*/3, f.weight_mode, w.cov, f.weight, nullptr,
+                        lds_limit, s);
+    if (rc != PBBSS_OK) return rc;
+    rc = launch_gen_heev(w.cov, (int64_t)nmat, D, -1, 0.0, w.eval, w.evec, f.status, lds_limit, s);
+    if (rc != PBBSS_OK) return rc;
+    rc = launch_gen_watson_finish(w.eval, w.evec, (int64_t)nmat, D, f.spline, f.mode, f.conc,
+                                  w.lognorm, s);
+    if (rc != PBBSS_OK) return rc;
+  }
+  if (f.final_predict && (f.out_affiliation || f.out_log_pdf))
+    return e_step(f.out_log_pdf ? f.out_log_pdf : w.lp, f.out_affiliation);
+  return PBBSS_OK;
 }
 
 }  // namespace pbbss

@@ -53,12 +53,6 @@ struct pbbss_handle_s {
 namespace pbbss {
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-inline int copy_d2d(void* dst, const void* src, size_t bytes, hipStream_t s) {
-  if (dst == src || bytes == 0) return PBBSS_OK;
-  return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess ? PBBSS_OK
-                                                                                   : PBBSS_ERR_HIP;
-}
-
 // standalone embedding entry points: K <= kEmbedMaxK on the kernels of embed.hip, beyond on the
 // class tiles of embed_wide.hip
 inline bool embed_shape_ok(int64_t B, int64_t N, int E, int K) {

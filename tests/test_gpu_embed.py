@@ -348,6 +348,30 @@ def test_gmm_shapes_against_oracle(F, N, E, K):
     np.testing.assert_allclose(m1.gaussian.mean, o1['mean'], atol=1e-9)
 
 
+def test_gmm_predict_from_a_model_with_log_pdf_output():
+    """pbbss_gmm_fit with iterations = 0 from a model, K <= 8, class log-pdfs next to the
+    posteriors (no trainer asks for both; the engine call does) against the oracle, at the
+    tolerances of the spherical log-pdf and of GMM.predict above; the model comes back as given."""
+    from oracle import embed as oe
+    from pb_bss_amd import _lib, engine
+    B, N, E, K = 2, 130, 5, 3
+    rng = np.random.default_rng(B * 100 + K)
+    y = rng.normal(size=(B, N, E))
+    mean = rng.normal(size=(B, K, E))
+    covariance = rng.uniform(0.5, 2.0, size=(B, K))
+    weight = rng.uniform(0.2, 1.0, size=(B, K))
+    weight /= weight.sum(-1, keepdims=True)
+    r = engine.gmm_fit(_lib.to_device(y), K, iterations=0, final_predict=True, want_log_pdf=True,
+                       model=tuple(_lib.to_device(a) for a in (mean, covariance, weight)))
+    for name, given in (('mean', mean), ('covariance', covariance), ('weight', weight)):
+        assert np.array_equal(_lib.to_host(r[name]), given), name
+    np.testing.assert_allclose(_lib.to_host(r['log_pdf']),
+                               oe.gaussian_log_pdf(y[:, None], mean, covariance),
+                               rtol=1e-10, atol=1e-9)
+    model = dict(mean=mean, covariance=covariance, weight=weight[..., None])
+    np.testing.assert_allclose(_lib.to_host(r['affiliation']), oe.gmm_predict(model, y), atol=1e-9)
+
+
 @pytest.mark.parametrize('N,E,K', [(20000, 40, 3), (333, 5, 2), (1000, 16, 6), (4100, 63, 1),
                                    (70, 17, 4), (600, 50, 3), (900, 10, 40), (500, 47, 2)])
 def test_gaussian_full_covariance_against_oracle(N, E, K):
@@ -592,6 +616,24 @@ def test_joint_sweep_wavefront_kernel_dimension_range(E, K):
         got = trainer.fit_predict(Y, e, initialization=init, iterations=4, saliency=sal, **kw)
         ref = oe.joint_fit(kind, Y128, e64, init, 4, saliency=sal, **kw)
         assert np.abs(got - oe.joint_model_predict(ref, Y128, e64)).max() < 1e-6, (E, K, kind)
+
+
+def test_joint_spectral_finalize_on_the_side_stream():
+    """2 K (E + 1) = 1068 values of the spectral model are more than the in-launch finalize of
+    the rotated joint loop takes (1024): the finalize kernel then runs on the handle's side
+    stream beside the spatial kernel (pbbss_joint_fit: fork after the sweep, join before the next
+    one).  Same oracle and bound as the sweep test above; T = 70: ragged tiles."""
+    from pb_bss_amd.distribution import GCACGMMTrainer, VMFCACGMMTrainer
+    from oracle import embed as oe, synth
+    F, T, D, K, E = 3, 70, 4, 6, 88
+    Y, e, init = synth.make_joint(F, T, D, K, E, seed=E + K)
+    Y128, e64 = Y.astype(np.complex128), e.astype(np.float64)
+    sal = np.random.default_rng(E).uniform(0.1, 1.0, size=(F, T))
+    for kind, trainer, kw in (('gaussian', GCACGMMTrainer(), {}),
+                              ('vmf', VMFCACGMMTrainer(), dict(max_concentration=80.))):
+        got = trainer.fit_predict(Y, e, initialization=init, iterations=4, saliency=sal, **kw)
+        ref = oe.joint_fit(kind, Y128, e64, init, 4, saliency=sal, **kw)
+        assert np.abs(got - oe.joint_model_predict(ref, Y128, e64)).max() < 1e-6, kind
 
 
 @pytest.mark.parametrize('T', [64, 65, 130, 257])

@@ -301,6 +301,36 @@ def test_watson_mixture_at_generic_sizes(F, T, D, K, with_sal):
     assert np.abs(m2.predict(Y) - ow.cwmm_predict(r2, Y128)).max() < 1e-6
 
 
+def test_watson_fit_resumed_from_a_model_at_generic_sizes():
+    """pbbss_cwmm_fit at generic sizes started from a model with iterations > 0 (no trainer does
+    that; the engine call does): 2 iterations from affiliations + 1 from the returned model ==
+    3 from affiliations == the oracle, at the multi-iteration tolerance of the test above.
+    T = 70: a ragged last tile."""
+    from pb_bss_amd import _lib, engine
+    from pb_bss_amd.distribution import CWMMTrainer
+    from oracle import cwmm as ow, synth
+    F, T, D, K = 3, 70, 9, 2
+    tol = 1e-6
+    Y, init = synth.make_stft(F, T, D, K, seed=D * 10 + K)
+    y, g0 = _lib.to_device(Y), _lib.to_device(init)
+    spline = CWMMTrainer(dimension=D).complex_watson_trainer.device_spline(y.device)
+    first = engine.cwmm_fit(y, K, spline, gamma0=g0, iterations=2)
+    model = (first['mode'], first['concentration'], first['weight'])
+    resumed = engine.cwmm_fit(y, K, spline, model=model, iterations=1, final_predict=True)
+    straight = engine.cwmm_fit(y, K, spline, gamma0=g0, iterations=3, final_predict=True)
+    Y128 = Y.astype(np.complex128)
+    ref = ow.cwmm_fit(Y128, init, iterations=3)
+    want = dict(ref, affiliation=ow.cwmm_predict(ref, Y128))
+    for other in ({k: _lib.to_host(v) for k, v in straight.items() if v is not None}, want):
+        got = {k: _lib.to_host(resumed[k]) for k in ('mode', 'concentration', 'weight',
+                                                     'affiliation')}
+        np.testing.assert_allclose(got['concentration'], other['concentration'], rtol=tol, atol=tol)
+        np.testing.assert_allclose(got['weight'], other['weight'].reshape(F, K), atol=tol)
+        assert np.abs(_cos_sim(got['mode'], other['mode']) - 1).max() < tol
+        assert np.abs(got['affiliation'] - other['affiliation']).max() < 100 * tol
+    assert int(_lib.to_host(resumed['status']).max()) == 0
+
+
 def test_watson_log_norm_for_many_sensors():
     """ln c(kappa) of the generic path (series of 1F1(1; D; kappa), all terms positive) against
     scipy over the whole range of the concentration spline."""
