@@ -1034,6 +1034,22 @@ int pbbss_stft(pbbss_handle_t h, const void* x, int x_is_f64, int64_t C, int64_t
 int pbbss_istft(pbbss_handle_t h, const void* X, int x_is_c128, int64_t C, int T, int size,
                 int shift, int window_length, const double* synthesis_window, int fading,
                 double* out, int64_t n_out, void* stream);
+/* GriffinLim.step / MISI.step  pb_bss/transform/griffin_lim_module.py:61-64, 106-130:
+ * `iterations` times  X'' = stft(x), X' = |X| exp(i angle X''), x_hat = istft(X')  with
+ * x = x_hat (Griffin-Lim, y NULL) or x = x_hat + (y - sum_k x_hat_k) / K (MISI, y (B, n)
+ * float64, K <= 8), as 2 launches per iteration on `stream` (MISI: one more in front) and no
+ * host synchronisation.  X (B, K, T, size/2+1) complex64 / complex128 gives the magnitudes;
+ * x_hat (B, K, n) float64 holds the current estimate on entry and the result on return;
+ * X_dash_dash and X_dash, both or neither NULL, receive X'' and X' of the last iteration as
+ * (B, K, T, size/2+1) complex128.  A bin of X'' that is exactly zero has the phase factor 1
+ * (numpy.angle(0) == 0).  The windows are those of pbbss_stft / pbbss_istft with
+ * window_length = size; size: power of two, size % shift == 0; iterations >= 1;
+ * n = T * shift + size - shift - (fading ? 2 (size - shift) : 0); B * K <= 65535. */
+int pbbss_griffin_lim(pbbss_handle_t h, const void* X, int x_is_c128, const double* y,
+                      int64_t B, int K, int T, int size, int shift,
+                      const double* analysis_window, const double* synthesis_window,
+                      int fading, int iterations, double* x_hat, void* X_dash_dash,
+                      void* X_dash, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* (W)  k-means on real embeddings: what BinaryGMM / BinaryGMMTrainer           */

@@ -220,6 +220,8 @@ SIGNATURES = {
     'pbbss_stft_num_frames': [i64, i32, i32, i32, i32, i32],
     'pbbss_stft': [vp, vp, i32, i64, i64, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp],
     'pbbss_istft': [vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, vp, i64, vp],
+    'pbbss_griffin_lim': [vp, vp, i32, vp, i64, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp,
+        i64, vp],
     'pbbss_pa_pairwise_mapping': [vp, vp, vp, i64, i32, i64, i32, vp, vp, i32, i32, vp, vp, i64,
         i64, vp, vp],
     'pbbss_pa_compose_mapping': [vp, vp, i64, i32, i64, vp],

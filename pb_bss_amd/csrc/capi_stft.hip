@@ -1,7 +1,8 @@
-// extern "C" boundary of the STFT edge (include/pbbss.h, N4; kernels: stft.hip): argument
-// validation and the workspace.  No device code lives here.
+// extern "C" boundary of the STFT edge (include/pbbss.h, N4; kernels: stft.hip, griffin_lim.hip):
+// argument validation and the workspace.  No device code lives here.
 #include "handle.hpp"
 #include "stft.hpp"
+#include "griffin_lim.hpp"
 
 using pbbss::as_stream, pbbss::DeviceGuard;
 
@@ -41,4 +42,24 @@ PBBSS_API int pbbss_istft(pbbss_handle_t h, const void* X, int x_is_c128, int64_
   return pbbss::launch_istft(X, x_is_c128, C, T, size, shift, window_length, synthesis_window, fade,
                              static_cast<double*>(wmem), out, n_out, h->cfg.lds_limit,
                              as_stream(stream));
+}
+
+PBBSS_API int pbbss_griffin_lim(pbbss_handle_t h, const void* X, int x_is_c128, const double* y,
+                                int64_t B, int K, int T, int size, int shift,
+                                const double* analysis_window, const double* synthesis_window,
+                                int fading, int iterations, double* x_hat, void* X_dash_dash,
+                                void* X_dash, int64_t n, void* stream) {
+  DeviceGuard device_guard(h);
+  if (!h || !X || !analysis_window || !synthesis_window || !x_hat || B <= 0 || K <= 0 || T <= 0 ||
+      iterations < 1)
+    return PBBSS_ERR_INVALID_ARG;
+  if ((X_dash_dash == nullptr) != (X_dash == nullptr)) return PBBSS_ERR_INVALID_ARG;
+  if (size < shift || shift < 1) return PBBSS_ERR_INVALID_ARG;
+  const int fade = fading ? size - shift : 0;
+  if (n != (int64_t)T * shift + size - shift - 2 * (int64_t)fade) return PBBSS_ERR_INVALID_ARG;
+  const pbbss::GriffinLimProblem p{X, x_is_c128, y, B, K, T, size, shift, fade, analysis_window,
+                                   synthesis_window, iterations, x_hat, X_dash_dash, X_dash, n};
+  void* wmem = h->work.grow(pbbss::griffin_lim_scratch_bytes(p));
+  if (!wmem) return PBBSS_ERR_HIP;
+  return pbbss::run_griffin_lim(p, wmem, h->cfg.lds_limit, as_stream(stream));
 }

@@ -19,59 +19,13 @@
 // HBM traffic is tiny next to the EM loop (one utterance: 3.1 MB out), so the kernels are
 // written for simplicity: the time is launch + LDS-latency bound, a few tens of microseconds.
 #include "stft.hpp"
+#include "fft_dev.hpp"
 #include "launch_util.hpp"
 #include <cmath>
 #include "pbbss_dev.hpp"
 
 namespace pbbss {
 namespace {
-
-constexpr int kStftThreads = 256;
-constexpr int kFramesPerWg = 4;
-
-struct Cplx {
-  double re, im;
-};
-
-__device__ __forceinline__ Cplx cmul(Cplx a, Cplx b) {
-  return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
-}
-
-// roots[k] = exp(-2 pi i k / N), k = 0..M (M = N/2)
-__device__ void build_roots(Cplx* roots, int N, int tid) {
-  const int M = N / 2;
-  for (int k = tid; k <= M; k += kStftThreads) {
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)N, &s, &c);
-    roots[k] = {c, s};
-  }
-}
-
-// In-LDS radix-2 Stockham FFT of M points (M a power of two >= 2).  SIGN = -1 forward,
-// +1 backward (unscaled).  Returns the buffer that holds the result.
-template <int SIGN>
-__device__ Cplx* stockham(Cplx* a, Cplx* b, const Cplx* roots, int M, int tid) {
-  int n = M, s = 1, ls = 0;  // s = 2^ls butterflies share a twiddle
-  while (n > 1) {
-    const int half = n >> 1;
-    for (int j = tid; j < (M >> 1); j += kStftThreads) {
-      const int p = j >> ls, q = j & (s - 1);
-      Cplx w = roots[2 * (p << ls)];  // exp(-2 pi i p / n) = roots_N[2 p M / n]
-      if (SIGN > 0) w.im = -w.im;
-      const Cplx u = a[q + s * p], v = a[q + s * (p + half)];
-      b[q + s * (2 * p)] = {u.re + v.re, u.im + v.im};
-      b[q + s * (2 * p + 1)] = cmul({u.re - v.re, u.im - v.im}, w);
-    }
-    __syncthreads();
-    Cplx* t = a;
-    a = b;
-    b = t;
-    n = half;
-    s <<= 1;
-    ++ls;
-  }
-  return a;
-}
 
 struct StftArgs {
   const void* x;        // (C, N) float32 / float64
@@ -236,8 +190,6 @@ __global__ void __launch_bounds__(kStftThreads) istft_ola_kernel(OlaArgs g) {
   for (int64_t t = t_lo; t <= t_hi; ++t) acc += g.frames[((size_t)c * g.T + t) * g.wl + (m - t * g.shift)];
   g.out[c * g.n_out + n] = acc;
 }
-
-bool pow2(int v) { return v >= 4 && (v & (v - 1)) == 0; }
 
 }  // namespace
 

@@ -1198,3 +1198,24 @@ def istft(X, size, shift, synthesis_window, *, fading=True):
                 synthesis_window, bool(fading), out, n_out,
                 what=f'istft(C={C},T={T},size={size},shift={shift},window_length={wl})')
     return out
+
+
+def griffin_lim(X, y, x_hat, size, shift, analysis_window, synthesis_window, *, fading=False,
+                iterations=1):
+    """pbbss_griffin_lim.  X (B,K,T,F) complex64/complex128, y (B,n) float64 (MISI) or None
+    (Griffin-Lim), x_hat (B,K,n) float64: the current estimate, left untouched.
+
+    Returns (x_hat, X_dash_dash, X_dash) after `iterations` iterations: (B,K,n) float64 and the
+    last iteration's two (B,K,T,F) complex128 spectra."""
+    t = _t()
+    B, K, T, F = X.shape
+    n = x_hat.shape[-1]
+    out = x_hat.clone()
+    X_dash_dash = t.empty((B, K, T, F), dtype=t.complex128, device=X.device)
+    X_dash = t.empty_like(X_dash_dash)
+    _lib.launch('pbbss_griffin_lim', X.device, X, X.dtype == t.complex128, y, B, K, T, size, shift,
+                analysis_window, synthesis_window, bool(fading), iterations, out, X_dash_dash,
+                X_dash, n,
+                what=f'griffin_lim(B={B},K={K},T={T},size={size},shift={shift},'
+                     f'iterations={iterations},misi={y is not None})')
+    return out, X_dash_dash, X_dash

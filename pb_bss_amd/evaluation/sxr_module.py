@@ -61,6 +61,14 @@ def _power(x, axis, keepdims):
     return out.reshape(kept_shape)
 
 
+def get_variance_for_zero_mean_signal(X, axis=None, keepdims=False):
+    """Mean of re^2 + im^2 over `axis` (sxr_module.py:17-23): the variance of a signal whose mean
+    is zero, real or complex, every axis by default.  float64."""
+    like_torch, home = _signals.home_of(X)
+    x = _signals.device_signal(X, complex_ok=True)
+    return _signals.result(_power(x, axis, keepdims), like_torch, home)
+
+
 def get_snr(X, N, *, axis=None, keepdims=False):
     """10 log10 of the power of `X` over the power of `N` (sxr_module.py:26-48), power being
     the mean of re^2 + im^2 over `axis` -- every axis by default, so arrays of any shape give one

@@ -1,8 +1,10 @@
 """STFT edge of the separation path: audio -> STFT -> (mixture model, beamformer) -> audio
 without leaving the device, and the gammatone filterbank of the
-reference's transform/gammatone.py."""
+reference's transform/gammatone.py, and the phase reconstruction (Griffin-Lim, MISI) of its
+transform/griffin_lim_module.py."""
 from .gammatone import gammatone_filterbank, calculate_cfs, Hz_2_ERBS, ERBS_2_Hz
 from .stft import stft, istft, stft_frames_to_samples, biorthogonal_window, analysis_window
+from .griffin_lim_module import GriffinLim, MISI
 
 __all__ = ['stft', 'istft', 'stft_frames_to_samples', 'biorthogonal_window', 'analysis_window',
-           'gammatone_filterbank', 'calculate_cfs', 'Hz_2_ERBS', 'ERBS_2_Hz']
+           'gammatone_filterbank', 'calculate_cfs', 'Hz_2_ERBS', 'ERBS_2_Hz', 'GriffinLim', 'MISI']
