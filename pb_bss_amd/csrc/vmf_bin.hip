@@ -100,7 +100,10 @@ __device__ __forceinline__ double wave_log_bessel_fixed(const double* tab, doubl
   for (int r = 0; r < kBesselRows; ++r) c[r] = tab[r * kWave + lane];  // in flight during the log
   const double q = 0.25 * x * x;
   // (log_pos / exp_nonpos, pbbss_dev.hpp: x is the clamped concentration -- finite, positive and
-  // normal, or NaN, which both propagate)
+  // normal, or NaN, which both propagate.  PRECONDITION: min_concentration >= tiny.  log_pos(0)
+  // is a finite number instead of -inf and the lanes with m0 > 0 would add spurious terms -- 5e-6
+  // of the offset at R = 1, E = 4, measured; VmfBin::run keeps a floor of 0 or of a denormal away
+  // from here.)
   const double lx = 2.0 * log_pos(x) - 1.3862943611198906;  // ln(x^2 / 4)
   const int m0 = lane * R;
   const double lt = (m0 ? (double)m0 * lx : 0.0) - c[0];
@@ -256,9 +259,11 @@ struct VmfBin {
     __syncthreads();
     const int nact = nchunk < NW ? nchunk : NW;  // waves that own at least one chunk
     // log-Bessel normaliser: fixed blocks while the clamp bounds the concentration (the default
-    // max_concentration is 500: R = 9), else the x-sized blocks of embed_dev.hpp
+    // max_concentration is 500: R = 9) and the floor keeps it a normal number, else the x-sized
+    // blocks of embed_dev.hpp (which reach the limit at x = 0 through IEEE log(0) = -inf)
     const double nu = 0.5 * E - 1.0;
-    const int bR = (a.cmax <= 960.0) ? ((int)ceil(fmax(a.cmax, 1.0)) + 48 + kWave - 1) / kWave : 0;
+    const int bR = (a.cmax <= 960.0 && a.cmin >= kTiny)
+                       ? ((int)ceil(fmax(a.cmax, 1.0)) + 48 + kWave - 1) / kWave : 0;
     if (bR > 0 && a.iterations > 0 && wave == NW - 1) bessel_table(btab, nu, bR, lane);
     // (visible to the class waves after the first iteration's barrier)
     for (int it = 0; it < a.iterations; ++it) {
@@ -351,9 +356,13 @@ struct VmfBin {
           tabs += fabs(s0[j]);
         }
         // (reciprocals by Newton steps, ~1 ulp: two IEEE divisions were ~60 dependent instructions
-        // of the workgroup's serial path; a zero class sum gives NaN either way)
+        // of the workgroup's serial path; a zero class sum gives NaN either way.  r_bar == 1 -- a
+        // class that sits on one point -- is (E - 1) / 0 = inf in the reference, clipped to the
+        // cap; the Newton steps would turn the estimate inf into NaN: selected around)
         const double rbar = norm * fast_rcp(s0k);                                       // eq. 2.5
-        double conc = (rbar * E - rbar * rbar * rbar) * fast_rcp(1.0 - rbar * rbar);  // eq. 4.4
+        const double omr = 1.0 - rbar * rbar;
+        const double romr = omr == 0.0 ? (double)INFINITY : fast_rcp(omr);
+        double conc = (rbar * E - rbar * rbar * rbar) * romr;                          // eq. 4.4
         conc = conc < a.cmin ? a.cmin : (conc > a.cmax ? a.cmax : conc);      // NaN stays NaN
         const double lb = bR > 0 ? wave_log_bessel_fixed(btab, nu, conc, lane, bR)
                                  : wave_log_bessel_over_power(nu, conc, lane);

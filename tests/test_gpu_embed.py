@@ -105,7 +105,8 @@ def test_vmfmm_shapes_against_oracle(N, E, K):
     (20, 300, 10, 3, np.float32, False), (257, 800, 12, 3, np.float32, False),
     (33, 257, 7, 2, np.float64, True), (16, 1200, 40, 5, np.float32, False),
     # round-6 kernel (vmf_bin.hip): four waves (<= 4 chunks), 64 accumulators with more
-    # mixtures than compute units (four waves), float64 rows at six waves, one chunk only
+    # mixtures than compute units (four waves), float64 rows in six chunks (B = 260 > 256 compute
+    # units: four waves again; eight are pinned in tests/test_gpu_vmf_bin.py), one chunk only
     (40, 200, 4, 4, np.float32, False), (300, 500, 14, 3, np.float32, True),
     (260, 330, 12, 2, np.float64, False), (17, 50, 16, 2, np.float32, False)])
 def test_vmfmm_many_small_mixtures_persistent_kernel(B, N, E, K, dtype, uniform):
