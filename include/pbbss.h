@@ -1134,6 +1134,41 @@ int pbbss_srmr_score(pbbss_handle_t h, const double* means, int64_t rows, int n,
                      const double* erbs, const double* cutoffs, double* out, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* (XI)  Polyphase resampler and short-time objective intelligibility, STOI     */
+/* (reference: evaluation/module_stoi.py, which wraps the pystoi package),      */
+/* float64 (csrc/stoi.hip).  Ordered sums, bit-identical from call to call; a   */
+/* call reads nothing back to the host.                                         */
+/*                                                                               */
+/* pbbss_resample_poly: rows float32 or float64 (is_f64), contiguous (rows, N),  */
+/* widened at the load.  out[r, m] = up * sum_n x[r, n] window[L + m down - n up] */
+/* with x zero outside its range, window of taps = 2 L + 1 doubles on the        */
+/* device, out (rows, ceil(N up / down)) float64: scipy.signal.resample_poly     */
+/* with a given window.                                                          */
+/* pbbss_stoi: outer * inner pairs of rows of N10 samples at 10 kHz; pair (o, i) */
+/* reads the clean row at x + o x_outer_stride + i x_inner_stride doubles and    */
+/* the processed row at y + o y_outer_stride + i y_inner_stride, samples         */
+/* consecutive; a stride may be 0 (broadcast).  Frames of 256 samples every 128  */
+/* (range(0, N10 - 256, 128)) under a Hann window; the frames of x within 40 dB  */
+/* of its loudest one are kept and overlap-added back to back, the same frames   */
+/* of y alike; a 512-point transform of the frames of both, 15 third-octave      */
+/* bands from 150 Hz, and the mean over all segments of 30 frames and all bands  */
+/* of the correlation of the clipped (-15 dB), centred, normalised band          */
+/* envelopes.  out (outer, inner) float64; a pair with fewer than 30 transform   */
+/* frames gives 1e-5.  out_frames, if not NULL, int32 (outer, inner, 2): the     */
+/* frames before and after the removal.                                          */
+/* PBBSS_ERR_UNSUPPORTED: more than 65535 rows or pairs, N, N10 or the resampled */
+/* length above 2^24.  PBBSS_ERR_INVALID_ARG: null pointers, sizes < 1, an even  */
+/* number of taps, a negative stride.                                            */
+/* ------------------------------------------------------------------------- */
+int pbbss_resample_poly(pbbss_handle_t h, const void* x, int is_f64, int64_t rows, int64_t N,
+                        int up, int down, const double* window, int taps, double* out,
+                        void* stream);
+int pbbss_stoi(pbbss_handle_t h, const double* x, const double* y, int64_t outer, int64_t inner,
+               int64_t N10, int64_t x_outer_stride, int64_t x_inner_stride,
+               int64_t y_outer_stride, int64_t y_inner_stride, double* out, int32_t* out_frames,
+               void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Timing hook for bench.py: runs `fit` with HIP events recorded on `stream`   */
 /* around the EM kernel launch(es) only and returns the elapsed milliseconds   */
 /* of the most recent call (the roofline figure needs the kernel duration on   */
