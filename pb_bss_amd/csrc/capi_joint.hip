@@ -151,7 +151,8 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
     gst = wc.take<int32_t>(16);                // status of the spectral half
     lndet = wc.take<double>((size_t)F * K);  // rotated loop: ln det B_fk of the current model
     fin_tmp = wc.take<double>((size_t)kJointFinHelpers * 2 * K * (E + 1));
-    gshift = wc.take<double>((size_t)E);  // sharded full covariance: the common shift
+    // sharded full covariance: the common shift of the first M-step
+    gshift = wc.take<double>(pbbss::gauss_full_column_sums_doubles(E));
     // generic-size spatial half: M-step weights, covariances, inverse state, class sums,
     // zero-frame flags, frame-contiguous copy of the observation
     g_mw = gen ? wc.take<double>(nfkt) : nullptr;
@@ -176,14 +177,12 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
     if (rc != PBBSS_OK) return rc;
   }
   if (sharded && g_full) {
-    // rank 0's first embedding row (converted to float64) on every rank
-    if (h->comm_rank == 0) {
-      rc = pbbss::launch_first_row_f64(embedding, o->embedding_is_f64, E, gshift, s);
-      if (rc != PBBSS_OK) return rc;
-    } else if (hipMemsetAsync(gshift, 0, (size_t)E * 8, s) != hipSuccess) {
-      return PBBSS_ERR_HIP;
-    }
-    if ((rc = all_ranks.fn(all_ranks.ctx, gshift, (size_t)E, s)) != PBBSS_OK) return rc;
+    // the first M-step has no previous means to centre on, and every rank must subtract the same
+    // point: the column mean of ALL ranks' embedding rows (column sums and row counts all-reduced)
+    rc = pbbss::launch_gauss_full_column_sums(embedding, o->embedding_is_f64, N, E, gshift, s);
+    if (rc != PBBSS_OK) return rc;
+    if ((rc = all_ranks.fn(all_ranks.ctx, gshift, (size_t)E + 1, s)) != PBBSS_OK) return rc;
+    if ((rc = pbbss::launch_gauss_full_column_mean(gshift, E, s)) != PBBSS_OK) return rc;
   }
   if (has_model) {
     if ((rc = copy_d2d(out_eigvec, in_eigvec, (size_t)F * K * D * D * 16, s)) != PBBSS_OK) return rc;
@@ -418,7 +417,8 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
       if ((rc = pbbss::launch_fkt_to_kn(src, saliency, F, K, T, wkn, s)) != PBBSS_OK) return rc;
       rc = pbbss::launch_gauss_full_fit(embedding, o->embedding_is_f64, 1, N, E, K, wkn, nullptr,
                                         gpart, out_mean, out_scale, mq, offset, nullptr, gst, s,
-                                        sharded ? gshift : nullptr, reduce);
+                                        it > 0 ? out_mean : nullptr,  // about the previous means
+                                        (sharded && it == 0) ? gshift : nullptr, reduce);
       mq_fresh = true;
     } else if (wide) {
       rc = pbbss::embed_wide_fit(o->kind, embedding, o->embedding_is_f64, 1, N, E, K, src, 0,
@@ -428,7 +428,7 @@ PBBSS_API int pbbss_joint_fit(pbbss_handle_t h, const void* observation, const v
       rc = pbbss::launch_embed_fit(o->kind, embedding, o->embedding_is_f64, 1, N, E, K, src, T,
                                    saliency, o->min_concentration, o->max_concentration, -1, part,
                                    out_mean, out_scale, nullptr, g_diag ? nullptr : offset,
-                                   g_diag ? nullptr : prec, it == 0 ? 2 : 1, s, nullptr, reduce);
+                                   g_diag ? nullptr : prec, it == 0 ? 0 : 1, s, nullptr, reduce);
     }
     if (rc != PBBSS_OK) return rc;
     if (fixed_scale) {  // fixed_covariance (gcacgmm.py:305-312)

@@ -20,9 +20,12 @@
 // read once from the caller's row-major array (float32 or float64, coalesced), widened and
 // shifted into an LDS tile, and every wavefront runs both contractions on its own 16 rows.  No
 // transposed copy, no (B, K, N) affiliation array between the two steps.
-//   y' = y - g with g the first row of the mixture (Gaussians: |y - m|^2 is expanded as
-//   |y'|^2 - 2 y'.m' + |m'|^2, and the second moment is taken about g and corrected in the
-//   finalize -- g lies within the data's spread, as the common shift of gauss_full.hip);
+//   y' = y - g with g the column mean of the mixture's rows, taken once per fit (Gaussians:
+//   |y - m|^2 is expanded as |y'|^2 - 2 y'.m' + |m'|^2, and the second moment is taken about g
+//   and corrected in the finalize.  The shifted tile is shared by all classes, so g cannot follow
+//   the classes: a class loses (|mean_k - g| / spread_k)^2 eps, which is small for clusters a few
+//   spreads apart and inherent for clusters far apart.  A weightless outlier moves g by its
+//   distance / N only, where any single row taken as g could BE the outlier);
 //   vMF: y' = y, the dot products and the M-step weights carry 1 / |y_n| (vmfmm.py:76-78) and the
 //   "1" column holds |y_n| so that the weight sums come out unscaled.
 // Accumulators: KT x ETW M-step tiles per wavefront with ETW <= 16 / KT (64 doubles per lane);
@@ -513,15 +516,53 @@ __global__ void __launch_bounds__(kWT)
   }
 }
 
-// g = first row of every mixture, padded to E4
-__global__ void wide_shift_kernel(const void* y, int y_is_f64, int64_t N, int E, int E4,
+// g = column mean of every mixture (unweighted: one g serves all classes and iterations), padded
+// to E4.  Stage 1, grid (C, B): thread t adds column t % E over the rows r, r + RL, ... of the
+// chunk (r = t / E, RL = 256 / E row lanes), the row lanes are added in order:
+// part[(b C + c) E + d], bit-reproducible.  Stage 2, one workgroup per mixture: chunks in order.
+static_assert(kEmbedMaxE <= kWT, "one thread per column");
+__global__ void __launch_bounds__(kWT)
+    wide_shift_part_kernel(const void* y, int y_is_f64, int64_t N, int E, int64_t L, double* part) {
+  __shared__ double red[kWT];
+  const int c = blockIdx.x, C = gridDim.x, tid = threadIdx.x;
+  const int64_t b = blockIdx.y;
+  const int RL = kWT / E, d = tid % E, r = tid / E;
+  const int64_t n0 = (int64_t)c * L;
+  const int64_t n1 = (n0 + L < N) ? n0 + L : N;
+  const size_t base = (size_t)b * N * E + d;
+  auto at = [&](int64_t n) {
+    return y_is_f64 ? static_cast<const double*>(y)[base + (size_t)n * E]
+                    : (double)static_cast<const float*>(y)[base + (size_t)n * E];
+  };
+  double t[4] = {0.0, 0.0, 0.0, 0.0};
+  if (r < RL) {
+    int64_t n = n0 + r;
+    for (; n + 3 * (int64_t)RL < n1; n += 4 * (int64_t)RL) {
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = at(n + (int64_t)u * RL);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) t[u] += v[u];
+    }
+    for (; n < n1; n += RL) t[0] += at(n);
+  }
+  red[tid] = (t[0] + t[1]) + (t[2] + t[3]);
+  __syncthreads();
+  if (tid < E) {
+    double v = 0.0;
+    for (int q = 0; q < RL; ++q) v += red[q * E + tid];
+    part[((size_t)b * C + c) * E + tid] = v;
+  }
+}
+__global__ void wide_shift_kernel(const double* part, int C, int64_t N, int E, int E4,
                                   double* shift) {
   const int64_t b = blockIdx.x;
   for (int d = threadIdx.x; d < E4; d += blockDim.x) {
     double v = 0.0;
-    if (d < E)
-      v = y_is_f64 ? static_cast<const double*>(y)[(size_t)b * N * E + d]
-                   : (double)static_cast<const float*>(y)[(size_t)b * N * E + d];
+    if (d < E) {
+      for (int c = 0; c < C; ++c) v += part[((size_t)b * C + c) * E + d];
+      v /= (double)N;
+    }
     shift[(size_t)b * E4 + d] = v;
   }
 }
@@ -749,7 +790,11 @@ int launch_wide_model(int kind, int64_t B, int E, int K, const WidePlan& p, cons
 int launch_wide_shift(int kind, const void* y, int y_is_f64, int64_t B, int64_t N, int E,
                       const WidePlan& p, const WideWork& w, hipStream_t s) {
   if (kind == PBBSS_EMBED_VMF) return PBBSS_OK;
-  hipLaunchKernelGGL(wide_shift_kernel, dim3((unsigned)B), dim3(kWT), 0, s, y, y_is_f64, N, E,
+  // the chunk sums (B, C, E) borrow the head of the sweep partials (B, C, K, EC): no sweep has
+  // run yet when the shift is taken
+  hipLaunchKernelGGL(wide_shift_part_kernel, dim3((unsigned)p.C, (unsigned)B), dim3(kWT), 0, s, y,
+                     y_is_f64, N, E, p.L, w.part);
+  hipLaunchKernelGGL(wide_shift_kernel, dim3((unsigned)B), dim3(kWT), 0, s, w.part, p.C, N, E,
                      p.E4, w.shift);
   return ok_or_hip();
 }

@@ -46,7 +46,7 @@ int embed_wide_log_pdf(int kind, const void* y, int y_is_f64, int64_t B, int64_t
                        double* work, double* out_lp, size_t lds_limit, hipStream_t s,
                        bool have_shift = false);
 
-// The Gaussians' common shift (first row of every mixture) into `work`, once per fit: a loop that
+// The Gaussians' common shift (column mean of every mixture) into `work`, once per fit: a loop that
 // calls embed_wide_fit / embed_wide_log_pdf on the SAME y and work passes have_shift = true.
 int embed_wide_shift(int kind, const void* y, int y_is_f64, int64_t B, int64_t N, int E, int K,
                      double* work, hipStream_t s);

@@ -5,12 +5,20 @@
 //
 // The weighted scatter  sum_n w_kn (y_n - mean_k)(y_n - mean_k)^T  is the one GEMM-shaped
 // piece of the whole library (E ~ 40: a 40 x N by N x 40 product per class), so it runs on the
-// FP64 matrix pipe: with the augmented, shifted vector z_n = [y_n - c ; 1 ; 0 ...] (c = first
-// row of the mixture, P = 16 NT entries) ONE symmetric Gram matrix
+// FP64 matrix pipe: with the augmented, shifted vector z_n = [y_n - c_k ; 1 ; 0 ...] (P = 16 NT
+// entries) ONE symmetric Gram matrix
 //     G_k = sum_n w_kn z_n z_n^T = [[S2', S1'], [S1'^T, S0]]
-// carries the second moment about c, the first moment about c and the weight sum; the finalize
-// turns them into mean and covariance about the mean (c within the data's spread: no
-// cancellation to speak of).  Tiles are v_mfma_f64_16x16x4_f64: lane l feeds A[i = l % 16]
+// carries the second moment about c_k, the first moment about c_k and the weight sum; the
+// finalize turns them into mean and covariance about the mean.  That subtraction loses
+// (|mean_k - c_k| / spread_k)^2 eps, so c_k has to lie within the spread of CLASS k: it is the
+// class's previous mean (EM iterations after the first), and where there is none the fit runs
+// twice -- first about row 0 of the mixture, which may be a weightless outlier or belong to
+// another cluster and only has to yield means good to eps |y - row 0|, then about those means.
+// A fit sharded over ranks cannot run twice that cheaply and every rank must subtract the same c
+// for the partial sums to add up: its first M-step is centred on the column mean of all ranks'
+// rows (capi_joint.hip), which a weightless outlier moves by its distance / N only, and the later
+// ones on the previous means, identical on every rank.
+// Tiles are v_mfma_f64_16x16x4_f64: lane l feeds A[i = l % 16]
 // [k = l / 16] and B[k = l / 16][j = l % 16] -- here sample k of a group of four, entries i / j
 // of two 16-blocks of z -- and holds D[4 r + l / 16][l % 16] in accumulator register r
 // (layout verified on the device by tools/ubench/mfma64.hip).  FP64 MFMA shares the FP64
@@ -46,7 +54,8 @@ template <int NT, typename TS>
 __global__ void __launch_bounds__(kGfThreads)
     gf_scatter_kernel(const TS* __restrict__ y, int64_t N, int E, int K,
                       const double* __restrict__ aff, const double* __restrict__ sal, int C,
-                      int64_t Lw, double* __restrict__ part, const double* __restrict__ gshift) {
+                      int64_t Lw, double* __restrict__ part, const double* __restrict__ gshift,
+                      const double* __restrict__ kshift) {
   constexpr int NTT = NT * (NT + 1) / 2;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -59,9 +68,11 @@ __global__ void __launch_bounds__(kGfThreads)
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int dim = 16 * t + i;
-    // c = row 0 of the mixture, or the caller's shift (bins sharded over ranks: every rank must
-    // subtract the SAME c for the partial sums to add up)
-    shift[t] = (dim < E) ? (gshift ? gshift[dim] : (double)yb[dim]) : 0.0;
+    // c = the class's centre (B,K,E), else the caller's common shift (bins sharded over ranks:
+    // every rank must subtract the SAME c for the partial sums to add up), else row 0
+    shift[t] = (dim < E) ? (kshift ? kshift[((size_t)b * K + k) * E + dim]
+                                   : (gshift ? gshift[dim] : (double)yb[dim]))
+                         : 0.0;
   }
   double4_t acc[NTT];
 #pragma unroll
@@ -330,9 +341,10 @@ __global__ void __launch_bounds__(kGfThreads)
 template <int NT, typename TS>
 __global__ void __launch_bounds__(kGfThreads)
     gf_finalize_kernel(const double* __restrict__ gsum, const TS* __restrict__ y, int64_t N,
-                       int E, int K, double* __restrict__ out_mean, double* __restrict__ out_cov,
+                       int E, int K, double* out_mean, double* __restrict__ out_cov,
                        double* out_mq, double* out_offset, double* out_s0,
-                       int32_t* out_status, const double* __restrict__ gshift) {
+                       int32_t* out_status, const double* __restrict__ gshift,
+                       const double* kshift) {  // kshift may BE out_mean: read, then written
   constexpr int NTT = NT * (NT + 1) / 2;
   constexpr int P = 16 * NT;
   extern __shared__ double sm[];
@@ -370,8 +382,14 @@ __global__ void __launch_bounds__(kGfThreads)
   if (out_s0 && tid == 0) out_s0[(size_t)b * K + k] = s0;
   double* mean = out_mean + ((size_t)b * K + k) * E;
   double* cov = out_cov + ((size_t)b * K + k) * (size_t)E * E;
-  for (int d = tid; d < E; d += kGfThreads)
-    mean[d] = (gshift ? gshift[d] : (double)yb[d]) + G[E * (P + 1) + d] / den;
+  // sum w y / den = c sum w / den + S1' / den: the factor is exactly 1 unless the class is empty
+  // (sum w < tiny), where the reference's 0 / tiny gives mean 0, not c
+  const double cfac = s0 / den;
+  for (int d = tid; d < E; d += kGfThreads) {
+    const double c = kshift ? kshift[((size_t)b * K + k) * E + d]
+                            : (gshift ? gshift[d] : (double)yb[d]);
+    mean[d] = c * cfac + G[E * (P + 1) + d] / den;
+  }
   for (int idx = tid; idx < E * E; idx += kGfThreads) {
     const int r = idx / E, cc = idx % E;
     // sum w (y - mean)(y - mean)^T with y - mean = (y - c) - m',  m' = S1' / den
@@ -610,7 +628,7 @@ template <int NT, typename TS>
 int gf_fit_go(const void* y, int64_t B, int64_t N, int E, int K, const double* w,
               const double* sal, double* part, double* out_mean, double* out_cov, double* out_mq,
               double* out_offset, double* out_s0, int32_t* out_status, hipStream_t s,
-              const double* gshift, const PartialReduce* reduce) {
+              const double* gshift, const double* kshift, const PartialReduce* reduce) {
   constexpr int P = 16 * NT;
   const int C = gf_chunks(B, K, N);
   int64_t Lw = (N + (int64_t)C * kGfWaves - 1) / ((int64_t)C * kGfWaves);
@@ -618,7 +636,7 @@ int gf_fit_go(const void* y, int64_t B, int64_t N, int E, int K, const double* w
   constexpr int NTT = NT * (NT + 1) / 2;
   hipLaunchKernelGGL((gf_scatter_kernel<NT, TS>), dim3((unsigned)C, (unsigned)K, (unsigned)B),
                      dim3(kGfThreads), (kGfWaves - 1) * NTT * 256 * sizeof(double), s,
-                     static_cast<const TS*>(y), N, E, K, w, sal, C, Lw, part, gshift);
+                     static_cast<const TS*>(y), N, E, K, w, sal, C, Lw, part, gshift, kshift);
   size_t ldsd = (size_t)P * (P + 1);
   if (out_mq && 2 * (size_t)E * (E + 1) > ldsd) ldsd = 2 * (size_t)E * (E + 1);
   const size_t lds = ldsd * sizeof(double);
@@ -632,7 +650,7 @@ int gf_fit_go(const void* y, int64_t B, int64_t N, int E, int K, const double* w
   }
   hipLaunchKernelGGL(kfn, dim3((unsigned)K, (unsigned)B), dim3(kGfThreads), lds, s, gsum,
                      static_cast<const TS*>(y), N, E, K, out_mean, out_cov, out_mq, out_offset,
-                     out_s0, out_status, gshift);
+                     out_s0, out_status, gshift, kshift);
   return gf_ok();
 }
 
@@ -682,13 +700,23 @@ int launch_gauss_full_fit(const void* y, int y_is_f64, int64_t B, int64_t N, int
                           const double* weights, const double* sal, double* part,
                           double* out_mean, double* out_cov, double* out_mq, double* out_offset,
                           double* out_s0, int32_t* out_status, hipStream_t s,
-                          const double* shift, const PartialReduce* reduce) {
+                          const double* centre, const double* shift,
+                          const PartialReduce* reduce) {
   if (E < 1 || E > kGaussFullMaxE || K < 1 || B < 1 || B > 65535 || K > 65535)
     return PBBSS_ERR_UNSUPPORTED;
   if ((shift || reduce) && B != 1) return PBBSS_ERR_INVALID_ARG;  // one mixture over the ranks
   return gf_dispatch(E, y_is_f64, [&](auto nt, auto ts) {
+    if (!centre && !shift && !reduce) {
+      // no centre yet: means about row 0 first (good to eps |y - row 0|), then the fit about them
+      int rc = gf_fit_go<nt(), decltype(ts)>(y, B, N, E, K, weights, sal, part, out_mean, out_cov,
+                                             nullptr, nullptr, nullptr, nullptr, s, nullptr,
+                                             nullptr, nullptr);
+      if (rc != PBBSS_OK) return rc;
+      centre = out_mean;
+    }
     return gf_fit_go<nt(), decltype(ts)>(y, B, N, E, K, weights, sal, part, out_mean, out_cov,
-                                         out_mq, out_offset, out_s0, out_status, s, shift, reduce);
+                                         out_mq, out_offset, out_s0, out_status, s, shift, centre,
+                                         reduce);
   });
 }
 
@@ -720,6 +748,71 @@ int launch_gauss_full_logpdf(const void* y, int y_is_f64, int64_t B, int64_t N, 
   });
 }
 
+// ------------------------------------------------------------------ centre of a sharded first fit
+// Column sums of a real (N, E) array in a fixed order.  Stage 1, grid (C): thread t adds column
+// t % E over the rows r, r + RL, ... of the chunk (r = t / E, RL = 256 / E row lanes), the row
+// lanes are added in order -> part[c E + d].  Stage 2, one workgroup: chunks in order -> out[d],
+// and the row count in out[E].
+namespace {
+static_assert(kGaussFullMaxE <= kGfThreads, "one thread per column");
+__global__ void __launch_bounds__(kGfThreads)
+    gf_column_sums_part_kernel(const void* y, int y_is_f64, int64_t N, int E, int64_t L,
+                               double* part) {
+  __shared__ double red[kGfThreads];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const int RL = kGfThreads / E, d = tid % E, r = tid / E;
+  const int64_t n0 = (int64_t)c * L;
+  const int64_t n1 = (n0 + L < N) ? n0 + L : N;
+  double t = 0.0;
+  if (r < RL)
+    for (int64_t n = n0 + r; n < n1; n += RL)
+      t += y_is_f64 ? static_cast<const double*>(y)[(size_t)n * E + d]
+                    : (double)static_cast<const float*>(y)[(size_t)n * E + d];
+  red[tid] = t;
+  __syncthreads();
+  if (tid < E) {
+    double v = 0.0;
+    for (int q = 0; q < RL; ++q) v += red[q * E + tid];
+    part[(size_t)c * E + tid] = v;
+  }
+}
+__global__ void gf_column_sums_kernel(const double* part, int C, int64_t N, int E, double* out) {
+  for (int d = threadIdx.x; d <= E; d += blockDim.x) {
+    double v = (double)N;
+    if (d < E) {
+      v = 0.0;
+      for (int c = 0; c < C; ++c) v += part[(size_t)c * E + d];
+    }
+    out[d] = v;
+  }
+}
+__global__ void gf_column_mean_kernel(double* v, int E) {
+  const int d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d < E) v[d] /= v[E];  // v[E], the row count, is read only
+}
+}  // namespace
+
+size_t gauss_full_column_sums_doubles(int E) { return (size_t)(kGfColumnSumChunks + 1) * E + 1; }
+
+int launch_gauss_full_column_sums(const void* y, int y_is_f64, int64_t N, int E, double* out,
+                                  hipStream_t s) {
+  if (E < 1 || E > kGaussFullMaxE || N < 1) return PBBSS_ERR_UNSUPPORTED;
+  int64_t C = (N + 1023) / 1024;
+  if (C > kGfColumnSumChunks) C = kGfColumnSumChunks;
+  const int64_t L = (N + C - 1) / C;
+  double* part = out + E + 1;
+  hipLaunchKernelGGL(gf_column_sums_part_kernel, dim3((unsigned)C), dim3(kGfThreads), 0, s, y,
+                     y_is_f64, N, E, L, part);
+  hipLaunchKernelGGL(gf_column_sums_kernel, dim3(1), dim3(kGfThreads), 0, s, part, (int)C, N, E,
+                     out);
+  return gf_ok();
+}
+
+int launch_gauss_full_column_mean(double* sums, int E, hipStream_t s) {
+  hipLaunchKernelGGL(gf_column_mean_kernel, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, s, sums,
+                     E);
+  return gf_ok();
+}
 
 int run_gmm_full_fit(const GmmFullFit& f, const GmmFullWork& w, hipStream_t s) {
   const int64_t B = f.B, N = f.N;
@@ -744,7 +837,8 @@ int run_gmm_full_fit(const GmmFullFit& f, const GmmFullWork& w, hipStream_t s) {
     }
     rc = launch_gauss_full_fit(f.y, f64, B, N, E, K, src, f.saliency, w.part, f.out_mean,
                                f.out_covariance, f.fixed_covariance ? nullptr : w.mq,
-                               f.fixed_covariance ? nullptr : w.off, w.s0, f.out_status, s);
+                               f.fixed_covariance ? nullptr : w.off, w.s0, f.out_status, s,
+                               it > 0 ? f.out_mean : nullptr);  // centre: the previous means
     if (rc != PBBSS_OK) return rc;
     rc = launch_gauss_full_weights(w.s0, B, K, f.weight_mode, f.out_weight, s);
     if (rc != PBBSS_OK) return rc;

@@ -22,10 +22,23 @@ int launch_gauss_full_fit(const void* y, int y_is_f64, int64_t B, int64_t N, int
                           const double* weights, const double* sal, double* part,
                           double* out_mean, double* out_cov, double* out_mq, double* out_offset,
                           double* out_s0, int32_t* out_status, hipStream_t s,
-                          // bins sharded over ranks (B = 1): `shift` (E) is the common centre c of
-                          // the augmented vectors (null: row 0 of y), `reduce` sums the Gram tiles
-                          // over the ranks between the reduction and the finalize kernel
-                          const double* shift = nullptr, const PartialReduce* reduce = nullptr);
+                          // `centre` (B,K,E; may be out_mean itself) is the point the moments of
+                          // each class are taken about: the previous means of an EM loop.  Null:
+                          // the fit runs twice, about row 0 of y and then about the means of that.
+                          // Bins sharded over ranks (B = 1): `shift` (E) is the common centre of a
+                          // first fit (no second run then), `reduce` sums the Gram tiles over the
+                          // ranks between the reduction and the finalize kernel
+                          const double* centre = nullptr, const double* shift = nullptr,
+                          const PartialReduce* reduce = nullptr);
+// The centre ranks share in the first M-step of a sharded fit: column sums of a real (N, E) array
+// and the row count, out[0..E) and out[E] (fixed summation order; `out` holds
+// gauss_full_column_sums_doubles(E), chunk partials behind the E + 1 results) -- summed over the
+// ranks, then launch_gauss_full_column_mean divides: out[0..E) = column mean of all ranks' rows.
+constexpr int kGfColumnSumChunks = 64;
+size_t gauss_full_column_sums_doubles(int E);
+int launch_gauss_full_column_sums(const void* y, int y_is_f64, int64_t N, int E, double* out,
+                                  hipStream_t s);
+int launch_gauss_full_column_mean(double* sums, int E, hipStream_t s);
 // mixture weights from the weight sums: mode 0 L1-normalised over the classes, 1 uniform
 int launch_gauss_full_weights(const double* s0, int64_t B, int K, int mode, double* out_weight,
                               hipStream_t s);

@@ -380,8 +380,10 @@ def test_gaussian_full_covariance_against_oracle(N, E, K):
     NumPy oracle (which is pinned to the reference by embed_single_fits): every tile count
     (E + 1 <= 16, 32, 48, 64; E + 1 = 48 exactly), ragged sample counts, float32 / float64
     input, no saliency; class counts beyond one LDS pass of whitening matrices (E = 50: one
-    class per pass; K = 40: two passes, one sample group per wave) and every per-thread
-    position count of the factorisation (E = 5 ... 63)."""
+    class per pass; K = 40: two passes, one sample group per wave) and four of the eight
+    per-thread position counts of the factorisation (Q = 1, 4, 5, 8).  Well-behaved input only
+    (cond(cov) ~ 1e2, unit scale, N >= 70); the other position counts, the shape edges and hard
+    input are in tests/test_gpu_gauss_full.py."""
     from oracle import embed as oe
     from pb_bss_amd.distribution import Gaussian, GaussianTrainer
     rng = np.random.default_rng(N + E)
