@@ -91,7 +91,9 @@ int pbbss_create(pbbss_handle_t* out, int device_id);
  * (pbbss_deflation_seed): fused for D <= 8, three launches per round around the generic
  * eigensolver for 9 <= D <= 32; 2 <= K <= 19; any T > 2 neighbors.  Oracle masks
  * (pbbss_mask_pointwise, pbbss_mask_lorenz, pbbss_mask_quantile): 1 <= K <= 9 sources,
- * 1 <= D <= 34 pooled sensors, up to 8 quantiles per call, rows of any length. */
+ * 1 <= D <= 34 pooled sensors, up to 8 quantiles per call, rows of any length.  Complex
+ * circular-symmetric Gaussian (pbbss_ccsg_fit, pbbss_ccsg_log_pdf): 1 <= D <= 34, any K >= 1,
+ * any N >= 1. */
 int pbbss_destroy(pbbss_handle_t h);
 
 /* ------------------------------------------------------------------------- */
@@ -1167,6 +1169,46 @@ int pbbss_stoi(pbbss_handle_t h, const double* x, const double* y, int64_t outer
                int64_t N10, int64_t x_outer_stride, int64_t x_inner_stride,
                int64_t y_outer_stride, int64_t y_inner_stride, double* out, int32_t* out_frames,
                void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* (XII)  Complex circular-symmetric Gaussian of a sensor vector                 */
+/* (distribution/complex_circular_symmetric_gaussian.py; csrc/ccsg.hip).         */
+/* y (B,N,D) c64 or c128 (y_is_c128) in the reference's own layout, 1 <= D <= 34, */
+/* any K >= 1, any N >= 1; float64 arithmetic on the exactly widened values.     */
+/*                                                                               */
+/* pbbss_ccsg_fit (ComplexCircularSymmetricGaussianTrainer._fit, :94-116):       */
+/* saliency (B,K,N) float32 or float64 (saliency_is_f64), or NULL (then K = 1),  */
+/* -> out_covariance (B,K,D,D) c128,                                             */
+/*   cov[b,k] = sum_n s[b,k,n] y[b,n,:] y[b,n,:]^H / max(sum_n s[b,k,n], floor)  */
+/* (:98-101; the host passes np.finfo(y.dtype).tiny), without saliency the sum   */
+/* over N.  The lower triangle is computed and mirrored: exactly Hermitian, real */
+/* diagonal.  Products are multiplied, never skipped (a NaN frame of zero        */
+/* saliency reaches the covariance); a zero saliency sum gives a zero matrix.    */
+/* y is read once for all K classes; rows longer than 256 frames (D <= 8) or 128 */
+/* are split over workgroups whose partial sums are added in a fixed order: the  */
+/* result is bit-identical from call to call.                                    */
+/*                                                                               */
+/* pbbss_ccsg_log_pdf (ComplexCircularSymmetricGaussian.log_pdf, :26-48):        */
+/* covariance (B,K,D,D) c128 -> out_log_pdf (B,K,N) f64                          */
+/*   = -D ln pi - ln det C - y^H C^-1 y,                                         */
+/* out_log_det (B,K) f64 or NULL, out_status (B,K) int32.  One launch: Cholesky  */
+/* C = L L^H once per covariance instead of the reference's LU per frame and     */
+/* class (:42-44), the quadratic form as |L^-1 y|^2 (never negative).  ONLY the  */
+/* lower triangle (row >= column) and the real part of the diagonal of each      */
+/* covariance are read, as by pbbss_heev_batched.  out_status:                   */
+/* PBBSS_ST_NOT_POSDEF where a pivot is <= 0 (singular or indefinite),           */
+/* PBBSS_ST_NONFINITE where that triangle holds a NaN or an Inf (or a pivot      */
+/* overflows); the log-pdf row and the log-determinant of such a matrix are NaN, */
+/* the other matrices of the call are unaffected.                                */
+/* PBBSS_ERR_UNSUPPORTED: D outside 1..34, more than 2^31 - 1 workgroups.        */
+/* PBBSS_ERR_INVALID_ARG: null pointers, B, N or K < 1, K != 1 without saliency. */
+/* ------------------------------------------------------------------------- */
+int pbbss_ccsg_fit(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int64_t N, int D,
+                   int K, const void* saliency, int saliency_is_f64, double floor,
+                   void* out_covariance, void* stream);
+int pbbss_ccsg_log_pdf(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int64_t N,
+                       int D, int K, const void* covariance, double* out_log_pdf,
+                       double* out_log_det, int32_t* out_status, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Timing hook for bench.py: runs `fit` with HIP events recorded on `stream`   */

@@ -260,6 +260,8 @@ SIGNATURES = {
     'pbbss_srmr_score': [vp, vp, i64, i32, vp, vp, vp, vp],
     'pbbss_resample_poly': [vp, vp, i32, i64, i64, i32, i32, vp, i32, vp, vp],
     'pbbss_stoi': [vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp],
+    'pbbss_ccsg_fit': [vp, vp, i32, i64, i64, i32, i32, vp, i32, dbl, vp, vp],
+    'pbbss_ccsg_log_pdf': [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -6,6 +6,10 @@ from .complex_angular_central_gaussian import (
     normalize_observation,
     sample_complex_angular_central_gaussian,
 )
+from .complex_circular_symmetric_gaussian import (
+    ComplexCircularSymmetricGaussian,
+    ComplexCircularSymmetricGaussianTrainer,
+)
 from .cacgmm import CACGMM, CACGMMTrainer, sample_cacgmm
 from .complex_watson import ComplexWatson, ComplexWatsonTrainer
 from .cwmm import CWMM, CWMMTrainer
@@ -27,5 +31,6 @@ __all__ = [
     'VMFCACGMM', 'VMFCACGMMTrainer',
     'ComplexWatson', 'ComplexWatsonTrainer',
     'ComplexAngularCentralGaussian', 'ComplexAngularCentralGaussianTrainer',
+    'ComplexCircularSymmetricGaussian', 'ComplexCircularSymmetricGaussianTrainer',
     'normalize_observation', 'sample_cacgmm', 'sample_complex_angular_central_gaussian',
 ]

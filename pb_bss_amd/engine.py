@@ -852,6 +852,66 @@ def gauss_full_log_pdf(y, mean, cov):
     return out, st
 
 
+# ---- complex circular-symmetric Gaussian: the shape plan of csrc/ccsg.hpp ----------------------
+CCSG_MAX_D = 34
+CCSG_SWEEP_D = (4, 8, 16, 34)   # log-pdf instantiations: the smallest bound that holds D
+CCSG_MAX_CLASS_TILE = 8         # classes in LDS at a time (fewer where D * D is large)
+CCSG_LDS = 160 * 1024
+
+
+def ccsg_frames(D):
+    """Frames per workgroup: a frame tile of the log-pdf, a span of the fit (longer rows are split
+    over workgroups)."""
+    return 256 if D <= 8 else 128
+
+
+def ccsg_class_tile(D):
+    """Classes whose Cholesky factors the log-pdf kernel holds in LDS beside its frame tile."""
+    frames = ccsg_frames(D) * (D | 1) * 16
+    per_class = D * D * 16 + D * 8 + 16
+    return min(CCSG_MAX_CLASS_TILE, (CCSG_LDS - frames) // per_class)
+
+
+def _ccsg_frames_arg(y):
+    t = _t()
+    assert y.ndim == 3 and y.dtype in (t.complex64, t.complex128), (y.shape, y.dtype)
+    return y.shape
+
+
+def ccsg_fit(y, saliency=None, floor=None):
+    """pbbss_ccsg_fit.  y (B,N,D) c64 / c128; saliency (B,K,N) f32 / f64 or None (K = 1); floor
+    of the saliency sum (default: the reference's np.finfo(y.dtype).tiny) -> (B,K,D,D) c128."""
+    t = _t()
+    B, N, D = _ccsg_frames_arg(y)
+    K = 1 if saliency is None else saliency.shape[1]
+    if saliency is not None:
+        assert saliency.shape == (B, K, N) and saliency.dtype in (t.float32, t.float64), (
+            saliency.shape, saliency.dtype, y.shape)
+    if floor is None:
+        floor = np.finfo(np.complex64 if y.dtype == t.complex64 else np.complex128).tiny
+    cov = t.empty((B, K, D, D), dtype=t.complex128, device=y.device)
+    _lib.launch('pbbss_ccsg_fit', y.device, y, y.dtype == t.complex128, B, N, D, K, saliency,
+                saliency is not None and saliency.dtype == t.float64, floor, cov,
+                what=f'ccsg_fit(B={B},N={N},D={D},K={K})')
+    return cov
+
+
+def ccsg_log_pdf(y, covariance, want_log_det=False):
+    """pbbss_ccsg_log_pdf.  y (B,N,D) c64 / c128; covariance (B,K,D,D) c128 (lower triangle and
+    real diagonal are read) -> (log_pdf (B,K,N), log_det (B,K) or None, status (B,K) int32)."""
+    t = _t()
+    B, N, D = _ccsg_frames_arg(y)
+    K = covariance.shape[1]
+    assert covariance.shape == (B, K, D, D) and covariance.dtype == t.complex128, (
+        covariance.shape, covariance.dtype, y.shape)
+    lp = t.empty((B, K, N), dtype=t.float64, device=y.device)
+    ld = t.empty((B, K), dtype=t.float64, device=y.device) if want_log_det else None
+    st = t.empty((B, K), dtype=t.int32, device=y.device)
+    _lib.launch('pbbss_ccsg_log_pdf', y.device, y, y.dtype == t.complex128, B, N, D, K,
+                covariance, lp, ld, st, what=f'ccsg_log_pdf(B={B},N={N},D={D},K={K})')
+    return lp, ld, st
+
+
 def gmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, weight_mode=0,
             fixed_covariance=None, final_predict=False, want_log_pdf=False):
     """pbbss_gmm_fit (spherical covariances).  y (B,N,E) real, used as given (no row
