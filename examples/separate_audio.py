@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Audio in -> audio out on one GPU, nothing but the waveforms crossing PCIe:
 
-    audio (D, samples) --stft('f t d')--> Y (F, T, D) --cACGMM EM--> masks --DHTV alignment-->
+    audio (D, samples) --stft('f t d')--> Y (F, T, D) [--WPE-->] --cACGMM EM--> masks --DHTV alignment-->
       PSD --'mvdr_souden' | 'gev+ban'--> beamformed STFT (K, T, F) --istft--> audio (K, samples)
 
-    python examples/separate_audio.py --seconds 8 --sensors 6 --sources 2
+    python examples/separate_audio.py --seconds 8 --sensors 6 --sources 2 [--wpe]
 
 Synthetic scene: `sources` on/off-modulated noise bursts through random short room filters
 plus sensor noise.  Prints the time per stage and, per source, the correlation of the best
@@ -52,6 +52,10 @@ def main():
                     help="recipe for get_bf_vector; the printed correlation compares with the source "
                          "image at sensor 0, so it is meaningful for distortionless recipes "
                          "('mvdr_souden', 'wmwf'), not for 'gev+ban' (free phase per bin)")
+    ap.add_argument('--wpe', action='store_true',
+                    help="dereverberate the STFT (pb_bss_amd.transform.wpe: 10 taps, delay 3, 3 "
+                         "iterations, read and written in the 'f t d' layout) in front of the "
+                         "mixture model and the beamformer")
     args = ap.parse_args()
     import torch
     from pb_bss_amd import initializer
@@ -59,7 +63,7 @@ def main():
     from pb_bss_amd.extraction import (apply_beamforming_vector, get_bf_vector,
                                        get_power_spectral_density_matrix)
     from pb_bss_amd.permutation_alignment import DHTVPermutationAlignment
-    from pb_bss_amd.transform import istft, stft
+    from pb_bss_amd.transform import istft, stft, wpe
 
     rng = np.random.default_rng(0)
     mix, images = make_scene(rng, args.seconds, args.rate, args.sensors, args.sources)
@@ -81,6 +85,9 @@ def main():
 
         Y = stft(x, args.size, args.shift, layout='f t d', dtype=np.complex64)   # (F, T, D)
         mark('stft')
+        if args.wpe:
+            Y = wpe(Y, layout='f t d')
+            mark('WPE 10 taps x3')
         if args.init == 'random':
             start = dict(num_classes=K)
         elif args.init == 'deflation':                                       # (K,F,T) -> (F,K,T) view

@@ -93,7 +93,8 @@ int pbbss_create(pbbss_handle_t* out, int device_id);
  * (pbbss_mask_pointwise, pbbss_mask_lorenz, pbbss_mask_quantile): 1 <= K <= 9 sources,
  * 1 <= D <= 34 pooled sensors, up to 8 quantiles per call, rows of any length.  Complex
  * circular-symmetric Gaussian (pbbss_ccsg_fit, pbbss_ccsg_log_pdf): 1 <= D <= 34, any K >= 1,
- * any N >= 1. */
+ * any N >= 1.  WPE dereverberation (pbbss_wpe and its parts): 1 <= D <= 16, D taps <= 96, any T
+ * and any number of problems. */
 int pbbss_destroy(pbbss_handle_t h);
 
 /* ------------------------------------------------------------------------- */
@@ -1209,6 +1210,60 @@ int pbbss_ccsg_fit(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, in
 int pbbss_ccsg_log_pdf(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int64_t N,
                        int D, int K, const void* covariance, double* out_log_pdf,
                        double* out_log_det, int32_t* out_status, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* XIII  WPE dereverberation (weighted prediction error; Nakatani et al. 2010, */
+/*       Drude et al. 2018, "NARA-WPE"; the offline functions of nara_wpe.wpe,  */
+/*       the package whose stft / istft signatures the reference imports)       */
+/* Frames are a strided (B, D, T) view: element (b, d, t) of `y` lies at        */
+/* b stride_b + d stride_d + t stride_t complex elements (c64 or c128), so the  */
+/* package's (..., D, T) and the (bins, frames, channels) the STFT writes are   */
+/* both read in place; out_x has the strides and the type of y.  B problems are */
+/* independent.  M = D taps; the stacked past of frame t is (y[t - delay],      */
+/* y[t - delay - 1], ..., y[t - delay - taps + 1]), tap-major, frames before 0  */
+/* are zeros.  Arithmetic is float64; R, P, G are c128; sums use ordered span   */
+/* partials (no atomics): results are bit-identical from call to call and a     */
+/* batch gives what its problems give one at a time.                            */
+/* pbbss_wpe (wpe): all iterations.  X = Y, then `iterations` times: power      */
+/*   p_t = mean_d |x_td|^2, smoothed over psd_context frames on either side     */
+/*   (0 = none, -1 = the mean over all frames); weights 1 / max(p_t, 1e-10      */
+/*   max_t p_t); R = sum_t w_t yt_t yt_t^H, P = sum_t w_t yt_t y_t^H over all   */
+/*   frames (PBBSS_WPE_STATISTICS_FULL) or t >= delay + taps - 1 (_VALID);      */
+/*   G = R^-1 P by Cholesky; x_t = y_t - G^H yt_t.  R and P always come from y. */
+/*   out_status (B): PBBSS_ST_NOT_POSDEF where a pivot of R is not positive or  */
+/*   not finite -- the rows of that problem in out_x are NaN, the others are    */
+/*   unaffected.  A problem whose frames are all zero gets G = 0 (x = 0).       */
+/* pbbss_wpe_power_inverse (get_power, get_power_inverse): out_power (B, T),    */
+/*   out_inverse_power (B, T) or null.  An all-zero row gets weight 0.          */
+/* pbbss_wpe_correlations (get_correlations): out_R (B, M, M) Hermitian to the  */
+/*   bit, out_P (B, M, D).                                                      */
+/* pbbss_wpe_filter_matrix (get_filter_matrix): G (B, M, D); only the lower     */
+/*   triangle and the real diagonal of R are read; G of a flagged problem: NaN. */
+/* pbbss_wpe_apply_filter (perform_filter_operation).                           */
+/* PBBSS_ERR_INVALID_ARG: null pointers, B, D, T, taps or iterations < 1,       */
+/*   delay < 0, psd_context < -1, an unknown statistics mode.                   */
+/* PBBSS_ERR_UNSUPPORTED: D > 16, D taps > 96, T or delay beyond 2^29.          */
+/* Nothing is written when an error code is returned.                           */
+/* ------------------------------------------------------------------------- */
+#define PBBSS_WPE_STATISTICS_FULL 0
+#define PBBSS_WPE_STATISTICS_VALID 1
+int pbbss_wpe(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int D, int64_t T,
+              int64_t stride_b, int64_t stride_d, int64_t stride_t, int taps, int delay,
+              int iterations, int64_t psd_context, int statistics_mode, void* out_x,
+              int32_t* out_status, void* stream);
+int pbbss_wpe_power_inverse(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int D,
+                            int64_t T, int64_t stride_b, int64_t stride_d, int64_t stride_t,
+                            int64_t psd_context, double* out_power, double* out_inverse_power,
+                            void* stream);
+int pbbss_wpe_correlations(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int D,
+                           int64_t T, int64_t stride_b, int64_t stride_d, int64_t stride_t,
+                           const double* inverse_power, int taps, int delay, int statistics_mode,
+                           void* out_R, void* out_P, void* stream);
+int pbbss_wpe_filter_matrix(pbbss_handle_t h, const void* R, const void* P, int64_t B, int D,
+                            int taps, void* out_G, int32_t* out_status, void* stream);
+int pbbss_wpe_apply_filter(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int D,
+                           int64_t T, int64_t stride_b, int64_t stride_d, int64_t stride_t,
+                           const void* G, int taps, int delay, void* out_x, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Timing hook for bench.py: runs `fit` with HIP events recorded on `stream`   */

@@ -262,6 +262,12 @@ SIGNATURES = {
     'pbbss_stoi': [vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp],
     'pbbss_ccsg_fit': [vp, vp, i32, i64, i64, i32, i32, vp, i32, dbl, vp, vp],
     'pbbss_ccsg_log_pdf': [vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp],
+    'pbbss_wpe': [vp, vp, i32, i64, i32, i64, i64, i64, i64, i32, i32, i32, i64, i32, vp, vp, vp],
+    'pbbss_wpe_power_inverse': [vp, vp, i32, i64, i32, i64, i64, i64, i64, i64, vp, vp, vp],
+    'pbbss_wpe_correlations': [vp, vp, i32, i64, i32, i64, i64, i64, i64, vp, i32, i32, i32, vp,
+        vp, vp],
+    'pbbss_wpe_filter_matrix': [vp, vp, vp, i64, i32, i32, vp, vp, vp],
+    'pbbss_wpe_apply_filter': [vp, vp, i32, i64, i32, i64, i64, i64, i64, vp, i32, i32, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 

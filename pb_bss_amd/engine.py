@@ -912,6 +912,142 @@ def ccsg_log_pdf(y, covariance, want_log_det=False):
     return lp, ld, st
 
 
+# ---- WPE dereverberation: the shape plan of csrc/wpe.hpp ----------------------------------------
+WPE_MAX_D = 16               # sensors
+WPE_MAX_M = 96               # stacked length D * taps
+WPE_TILE = 16                # edge of an FP64 MFMA tile of the correlation kernel
+WPE_SPAN = 128               # frames per workgroup of the correlation kernel (ordered span sums)
+WPE_CORR_TILES = (2, 4, 7)   # correlation instantiations: accumulator tiles per wavefront
+WPE_APPLY_FRAMES = 256       # frames per workgroup of the filter kernel
+WPE_APPLY_D = (4, 8, 16)     # filter instantiations: the smallest bound that holds D
+WPE_LDS = 160 * 1024
+WPE_STATISTICS = {'full': 0, 'valid': 1}
+
+
+def wpe_tiles(D, taps):
+    """Tiles of the lower block triangle of the extended (D * taps + D)-row Gram matrix."""
+    blocks = -(-(D * taps + D) // WPE_TILE)
+    return blocks * (blocks + 1) // 2
+
+
+def wpe_corr_tiles_per_wave(D, taps):
+    """Accumulator tiles a wavefront of the correlation kernel holds (four share the triangle)."""
+    return -(-wpe_tiles(D, taps) // 4)
+
+
+def wpe_solve_lds(D, taps):
+    """LDS of the solver: packed lower triangle of R, the D columns of P, reciprocal diagonal."""
+    M = D * taps
+    return (M * (M + 1) // 2 + M * D) * 16 + M * 8
+
+
+def _wpe_frames(y):
+    """y: a (B, D, T) view (any strides) of c64 / c128 frames -> (view the kernels can read,
+    the leading arguments of the exports)."""
+    t = _t()
+    assert y.ndim == 3 and y.dtype in (t.complex64, t.complex128), (tuple(y.shape), y.dtype)
+    assert y.is_cuda and y.shape[0] >= 1 and y.shape[1] >= 1 and y.shape[2] >= 1, tuple(y.shape)
+    if not (y.is_contiguous() or y.transpose(1, 2).is_contiguous()):
+        y = y.contiguous()
+    B, D, T = y.shape
+    sb, sd, st = y.stride()
+    return y, (_lib.view_ptr(y), y.dtype == t.complex128, B, D, T, sb, sd, st)
+
+
+def _wpe_served(D, taps, delay):
+    if D > WPE_MAX_D:
+        raise NotImplementedError(f'wpe: D = {D} sensors, served up to WPE_MAX_D = {WPE_MAX_D}')
+    if taps >= 1 and D * taps > WPE_MAX_M:
+        raise NotImplementedError(
+            f'wpe: D * taps = {D * taps}, served up to WPE_MAX_M = {WPE_MAX_M}')
+    assert taps >= 1 and delay >= 0, (taps, delay)
+
+
+def _wpe_context(psd_context):
+    if psd_context == float('inf'):
+        return -1
+    assert psd_context >= 0 and int(psd_context) == psd_context, psd_context
+    return int(psd_context)
+
+
+def _wpe_like(y):
+    """An uninitialised tensor with the shape and the strides of y."""
+    return _t().empty_strided(tuple(y.shape), tuple(y.stride()), dtype=y.dtype, device=y.device)
+
+
+def wpe(y, taps, delay, iterations, psd_context=0, statistics_mode='full'):
+    """pbbss_wpe.  y: (B, D, T) view -> (x with the strides and dtype of y, status (B,) int32)."""
+    y, head = _wpe_frames(y)
+    B, D = y.shape[:2]
+    _wpe_served(D, taps, delay)
+    assert iterations >= 1, iterations
+    x = _wpe_like(y)
+    st = _t().empty((B,), dtype=_t().int32, device=y.device)
+    _lib.launch('pbbss_wpe', y.device, *head, taps, delay, iterations, _wpe_context(psd_context),
+                WPE_STATISTICS[statistics_mode], _lib.view_ptr(x), st,
+                what=f'wpe(B={B},D={D},T={y.shape[2]},taps={taps},delay={delay})')
+    return x, st
+
+
+def wpe_power(y, psd_context=0, inverse=True):
+    """pbbss_wpe_power_inverse.  y: (B, D, T) view -> (power (B, T), inverse power or None)."""
+    t = _t()
+    y, head = _wpe_frames(y)
+    if y.shape[1] > WPE_MAX_D:
+        _wpe_served(y.shape[1], 1, 0)
+    B, _, T = y.shape
+    power = t.empty((B, T), dtype=t.float64, device=y.device)
+    inv = t.empty((B, T), dtype=t.float64, device=y.device) if inverse else None
+    _lib.launch('pbbss_wpe_power_inverse', y.device, *head, _wpe_context(psd_context), power, inv,
+                what=f'wpe_power(B={B},D={y.shape[1]},T={T})')
+    return power, inv
+
+
+def wpe_correlations(y, inverse_power, taps, delay, statistics_mode='full'):
+    """pbbss_wpe_correlations.  y: (B, D, T) view; inverse_power (B, T) f64 ->
+    (R (B, M, M), P (B, M, D)) c128, M = D * taps."""
+    t = _t()
+    y, head = _wpe_frames(y)
+    B, D, T = y.shape
+    _wpe_served(D, taps, delay)
+    assert inverse_power.shape == (B, T) and inverse_power.dtype == t.float64, (
+        tuple(inverse_power.shape), inverse_power.dtype, tuple(y.shape))
+    M = D * taps
+    R = t.empty((B, M, M), dtype=t.complex128, device=y.device)
+    P = t.empty((B, M, D), dtype=t.complex128, device=y.device)
+    _lib.launch('pbbss_wpe_correlations', y.device, *head, inverse_power.contiguous(), taps, delay,
+                WPE_STATISTICS[statistics_mode], R, P,
+                what=f'wpe_correlations(B={B},D={D},T={T},taps={taps},delay={delay})')
+    return R, P
+
+
+def wpe_filter_matrix(R, P):
+    """pbbss_wpe_filter_matrix.  R (B, M, M), P (B, M, D) c128 -> (G (B, M, D), status (B,))."""
+    t = _t()
+    B, M, D = P.shape
+    assert R.shape == (B, M, M) and R.dtype == P.dtype == t.complex128 and M % D == 0, (
+        tuple(R.shape), tuple(P.shape), R.dtype, P.dtype)
+    _wpe_served(D, M // D, 0)
+    G = t.empty((B, M, D), dtype=t.complex128, device=P.device)
+    st = t.empty((B,), dtype=t.int32, device=P.device)
+    _lib.launch('pbbss_wpe_filter_matrix', P.device, R.contiguous(), P.contiguous(), B, D, M // D,
+                G, st, what=f'wpe_filter_matrix(B={B},M={M},D={D})')
+    return G, st
+
+
+def wpe_apply_filter(y, G, taps, delay):
+    """pbbss_wpe_apply_filter.  y: (B, D, T) view; G (B, D * taps, D) c128 -> x like y."""
+    t = _t()
+    y, head = _wpe_frames(y)
+    B, D, T = y.shape
+    _wpe_served(D, taps, delay)
+    assert G.shape == (B, D * taps, D) and G.dtype == t.complex128, (tuple(G.shape), G.dtype)
+    x = _wpe_like(y)
+    _lib.launch('pbbss_wpe_apply_filter', y.device, *head, G.contiguous(), taps, delay,
+                _lib.view_ptr(x), what=f'wpe_apply_filter(B={B},D={D},T={T},taps={taps})')
+    return x
+
+
 def gmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, weight_mode=0,
             fixed_covariance=None, final_predict=False, want_log_pdf=False):
     """pbbss_gmm_fit (spherical covariances).  y (B,N,E) real, used as given (no row
