@@ -4,7 +4,7 @@
     audio (D, samples) --stft('f t d')--> Y (F, T, D) [--WPE-->] --cACGMM EM--> masks --DHTV alignment-->
       PSD --'mvdr_souden' | 'gev+ban'--> beamformed STFT (K, T, F) --istft--> audio (K, samples)
 
-    python examples/separate_audio.py --seconds 8 --sensors 6 --sources 2 [--wpe]
+    python examples/separate_audio.py --seconds 8 --sensors 6 --sources 2 [--wpe [recursive]]
 
 Synthetic scene: `sources` on/off-modulated noise bursts through random short room filters
 plus sensor noise.  Prints the time per stage and, per source, the correlation of the best
@@ -52,10 +52,12 @@ def main():
                     help="recipe for get_bf_vector; the printed correlation compares with the source "
                          "image at sensor 0, so it is meaningful for distortionless recipes "
                          "('mvdr_souden', 'wmwf'), not for 'gev+ban' (free phase per bin)")
-    ap.add_argument('--wpe', action='store_true',
-                    help="dereverberate the STFT (pb_bss_amd.transform.wpe: 10 taps, delay 3, 3 "
-                         "iterations, read and written in the 'f t d' layout) in front of the "
-                         "mixture model and the beamformer")
+    ap.add_argument('--wpe', nargs='?', const='offline', choices=('offline', 'recursive'),
+                    help="dereverberate the STFT in front of the mixture model and the beamformer, "
+                         "read and written in the 'f t d' layout, 10 taps, delay 3: 'offline' "
+                         "(the default of a bare --wpe; pb_bss_amd.transform.wpe, 3 iterations) "
+                         "or 'recursive' (transform.recursive_wpe: one filter update per frame, "
+                         "alpha 0.9999)")
     args = ap.parse_args()
     import torch
     from pb_bss_amd import initializer
@@ -63,7 +65,7 @@ def main():
     from pb_bss_amd.extraction import (apply_beamforming_vector, get_bf_vector,
                                        get_power_spectral_density_matrix)
     from pb_bss_amd.permutation_alignment import DHTVPermutationAlignment
-    from pb_bss_amd.transform import istft, stft, wpe
+    from pb_bss_amd.transform import istft, recursive_wpe, stft, wpe
 
     rng = np.random.default_rng(0)
     mix, images = make_scene(rng, args.seconds, args.rate, args.sensors, args.sources)
@@ -85,7 +87,10 @@ def main():
 
         Y = stft(x, args.size, args.shift, layout='f t d', dtype=np.complex64)   # (F, T, D)
         mark('stft')
-        if args.wpe:
+        if args.wpe == 'recursive':
+            Y = recursive_wpe(Y, layout='f t d')
+            mark('recursive WPE 10 taps')
+        elif args.wpe:
             Y = wpe(Y, layout='f t d')
             mark('WPE 10 taps x3')
         if args.init == 'random':

@@ -1265,6 +1265,36 @@ int pbbss_wpe_apply_filter(pbbss_handle_t h, const void* y, int y_is_c128, int64
                            int64_t T, int64_t stride_b, int64_t stride_d, int64_t stride_t,
                            const void* G, int taps, int delay, void* out_x, void* stream);
 
+/* pbbss_wpe_online (online_wpe_step, recursive_wpe, OnlineWPE): T frames of the   */
+/*   frame-recursive form for B independent problems, one recursive-least-squares  */
+/*   update per frame, in this order (ytilde_t as above, frames before the stream  */
+/*   are zeros):                                                                   */
+/*     x_t = y_t - G^H ytilde_t        n = P ytilde_t                               */
+/*     den = alpha lambda_t + Re(ytilde_t^H n)                                      */
+/*     k   = n (1 / den), or 0 where den is not > 0                                 */
+/*     P  <- (P - k n^H) (1 / alpha)   lower triangle, real diagonal; the upper     */
+/*                                     triangle is the conjugate mirror             */
+/*     G  <- G + k x_t^H                                                            */
+/*   lambda_t = power_estimate[b, t] (float64 (B, T)), or with a null pointer the   */
+/*   mean of |y|^2 over the sensors and the frames t - taps - delay .. t of the     */
+/*   stream that exist, summed in ascending frame order.                            */
+/*   State, read and written in place: inv_cov (B, M, M) c128 (the lower triangle   */
+/*   and the real diagonal are read, the whole matrix is written, Hermitian to the  */
+/*   bit), filter_taps (B, M, D) c128, history (B, D, taps + delay) c128 (the last  */
+/*   frames of the stream, newest last; zeros before it), frames_seen (B) int64.    */
+/*   A stream starts from P = I, G = 0, history = 0, frames_seen = 0; cutting it    */
+/*   into calls of any lengths gives bit for bit what one call gives.               */
+/*   out_status (B): PBBSS_ST_NONFINITE where den, x, P or G stopped being finite:  */
+/*   out_x of that problem is NaN from that frame on, as are its P and G.           */
+/* PBBSS_ERR_INVALID_ARG: null pointers (power_estimate may be null), B, D, T or    */
+/*   taps < 1, delay < 0, alpha outside (0, 1].  PBBSS_ERR_UNSUPPORTED: D > 16,     */
+/*   D taps > 96, D (taps + delay) > 2048, T beyond 2^29, B beyond 2^31 - 1.        */
+int pbbss_wpe_online(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int D, int64_t T,
+                     int64_t stride_b, int64_t stride_d, int64_t stride_t, int taps, int delay,
+                     double alpha, const double* power_estimate, void* inv_cov,
+                     void* filter_taps, void* history, int64_t* frames_seen, void* out_x,
+                     int32_t* out_status, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Timing hook for bench.py: runs `fit` with HIP events recorded on `stream`   */
 /* around the EM kernel launch(es) only and returns the elapsed milliseconds   */

@@ -268,6 +268,8 @@ SIGNATURES = {
         vp, vp],
     'pbbss_wpe_filter_matrix': [vp, vp, vp, i64, i32, i32, vp, vp, vp],
     'pbbss_wpe_apply_filter': [vp, vp, i32, i64, i32, i64, i64, i64, i64, vp, i32, i32, vp, vp],
+    'pbbss_wpe_online': [vp, vp, i32, i64, i32, i64, i64, i64, i64, i32, i32, dbl, vp, vp, vp, vp,
+        vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 

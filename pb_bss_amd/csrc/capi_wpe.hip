@@ -2,6 +2,7 @@
 // argument validation, the workspace and the chain of launches.  No device code lives here.
 #include "handle.hpp"
 #include "wpe.hpp"
+#include "wpe_online.hpp"
 
 using pbbss::as_stream, pbbss::DeviceGuard, pbbss::TimedRegion, pbbss::WpeFrames, pbbss::WpeWork;
 
@@ -170,4 +171,28 @@ PBBSS_API int pbbss_wpe_apply_filter(pbbss_handle_t h, const void* y, int y_is_c
   return pbbss::launch_wpe_apply(frames(y, y_is_c128, D, T, stride_b, stride_d, stride_t), B,
                                  static_cast<const double*>(G), taps, delay, out_x, nullptr,
                                  as_stream(stream));
+}
+
+PBBSS_API int pbbss_wpe_online(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int D,
+                               int64_t T, int64_t stride_b, int64_t stride_d, int64_t stride_t,
+                               int taps, int delay, double alpha, const double* power_estimate,
+                               void* inv_cov, void* filter_taps, void* history,
+                               int64_t* frames_seen, void* out_x, int32_t* out_status,
+                               void* stream) {
+  DeviceGuard device_guard(h);
+  int rc = check_frames(y, B, D, T);
+  if (!h || !inv_cov || !filter_taps || !history || !frames_seen || !out_x || !out_status ||
+      rc == PBBSS_ERR_INVALID_ARG || taps < 1 || delay < 0 || !(alpha > 0.0 && alpha <= 1.0))
+    return PBBSS_ERR_INVALID_ARG;
+  if (rc == PBBSS_OK) rc = check_taps(D, taps, delay);
+  if (rc != PBBSS_OK) return rc;
+  if (B > INT32_MAX || (int64_t)D * ((int64_t)taps + delay) > pbbss::kWpeOnlineMaxRing)
+    return PBBSS_ERR_UNSUPPORTED;
+  if (h->cfg.lds_limit && h->cfg.lds_limit < pbbss::kWpeLds) return PBBSS_ERR_LDS_CAPACITY;
+  TimedRegion tr(h, as_stream(stream));
+  const pbbss::WpeOnlineState st{power_estimate, static_cast<double*>(inv_cov),
+                                 static_cast<double*>(filter_taps), static_cast<double*>(history),
+                                 frames_seen};
+  return pbbss::launch_wpe_online(frames(y, y_is_c128, D, T, stride_b, stride_d, stride_t), B, taps,
+                                  delay, alpha, st, out_x, out_status, as_stream(stream));
 }

@@ -1048,6 +1048,55 @@ def wpe_apply_filter(y, G, taps, delay):
     return x
 
 
+# the frame-recursive form: the shape plan of csrc/wpe_online.hpp
+WPE_ONLINE_TILE = 32         # frames staged, and output frames written, at a time
+WPE_ONLINE_MAX_RING = 2048   # D * (taps + delay): the frames kept behind the stream
+
+
+def wpe_online_lds(D, taps, delay):
+    """LDS of the recursive kernel: packed triangle of P, G, the frames behind the stream and a
+    tile of them, a tile of output, n and x, a tile of lambda."""
+    M = D * taps
+    return (M * (M + 1) // 2 + M * D + (taps + delay + 2 * WPE_ONLINE_TILE) * D + M
+            + WPE_MAX_D) * 16 + WPE_ONLINE_TILE * 8
+
+
+def wpe_online_served(D, taps, delay):
+    _wpe_served(D, taps, delay)
+    if D * (taps + delay) > WPE_ONLINE_MAX_RING:
+        raise NotImplementedError(f'recursive wpe: D * (taps + delay) = {D * (taps + delay)}, '
+                                  f'served up to WPE_ONLINE_MAX_RING = {WPE_ONLINE_MAX_RING}')
+
+
+def wpe_online(y, taps, delay, alpha, power_estimate, inv_cov, filter_taps, history, frames_seen):
+    """pbbss_wpe_online.  y: (B, D, T) view; power_estimate (B, T) f64 or None; the state --
+    inv_cov (B, M, M), filter_taps (B, M, D), history (B, D, taps + delay) c128, frames_seen (B,)
+    int64 -- is updated in place -> (x with the strides and dtype of y, status (B,) int32)."""
+    t = _t()
+    y, head = _wpe_frames(y)
+    B, D, T = y.shape
+    wpe_online_served(D, taps, delay)
+    assert 0.0 < alpha <= 1.0, alpha
+    M, H = D * taps, taps + delay
+    assert inv_cov.shape == (B, M, M) and filter_taps.shape == (B, M, D) and \
+        history.shape == (B, D, H) and frames_seen.shape == (B,), (
+            tuple(inv_cov.shape), tuple(filter_taps.shape), tuple(history.shape),
+            tuple(frames_seen.shape), tuple(y.shape))
+    assert inv_cov.dtype == filter_taps.dtype == history.dtype == t.complex128 and \
+        frames_seen.dtype == t.int64, (inv_cov.dtype, filter_taps.dtype, history.dtype,
+                                       frames_seen.dtype)
+    if power_estimate is not None:
+        assert power_estimate.shape == (B, T) and power_estimate.dtype == t.float64, (
+            tuple(power_estimate.shape), power_estimate.dtype, tuple(y.shape))
+        power_estimate = power_estimate.contiguous()
+    x = _wpe_like(y)
+    st = t.empty((B,), dtype=t.int32, device=y.device)
+    _lib.launch('pbbss_wpe_online', y.device, *head, taps, delay, alpha, power_estimate, inv_cov,
+                filter_taps, history, frames_seen, _lib.view_ptr(x), st,
+                what=f'wpe_online(B={B},D={D},T={T},taps={taps},delay={delay})')
+    return x, st
+
+
 def gmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, weight_mode=0,
             fixed_covariance=None, final_predict=False, want_log_pdf=False):
     """pbbss_gmm_fit (spherical covariances).  y (B,N,E) real, used as given (no row
