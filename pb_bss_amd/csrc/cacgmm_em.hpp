@@ -599,8 +599,10 @@ struct EmKernel {
         // with q = m 2^e: one reciprocal of the mantissa serves both 1/q (M-step
         // weight) and q^-D = (1/m)^D 2^(-eD); 1/det_k is precomputed per class.
         double val[K], rq[K];
-        int ex[K];
-        int emax = INT32_MIN;
+        // exponent of class k's density is -(e D + dete): kept with the sign flipped, so that the
+        // shift against the largest one is emin - nex[k] -- one subtraction per class, no negation
+        int nex[K];
+        int emin = INT32_MAX;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
           double qq = fmax(fabs(q[f][k] * inv), kTiny);  // cacg.py:185-199
@@ -610,8 +612,8 @@ struct EmKernel {
           double rm = fast_rcp(m);            // m in [0.5, 1)
           rq[k] = ldexp(rm, -e);              // 1/q (finite: q >= tiny)
           val[k] = rdet[k] * ipow<D>(rm);
-          ex[k] = -(e * D + dete[k]);
-          emax = max(emax, ex[k]);
+          nex[k] = e * D + dete[k];
+          emin = min(emin, nex[k]);
         }
         double g[K], den = 0.0;
 #pragma unroll
@@ -624,12 +626,16 @@ struct EmKernel {
           } else {
             w = wgt[k];
           }
-          double v = ldexp(val[k], ex[k] - emax) * w;  // mixture_model_utils.py:32-37
-          const uint8_t* act = FINAL ? a.final_activity : a.activity;
-          if (act) v *= (double)act[((size_t)b * K + k) * TS + tf + t];
-          g[k] = v;
-          den += v;
+          g[k] = ldexp(val[k], emin - nex[k]) * w;  // mixture_model_utils.py:32-37
         }
+        // source activity mask: one wave-uniform test around the K loads (inside the loop above it
+        // compiled to a branch and a multiplication by 1.0 per class when there is no mask)
+        if (const uint8_t* act = FINAL ? a.final_activity : a.activity) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) g[k] *= (double)act[((size_t)b * K + k) * TS + tf + t];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) den += g[k];
         // np.maximum and np.clip keep a NaN (mixture_model_utils.py:43-53), v_max / v_min drop it:
         // a non-finite class sum (NaN weights, a NaN model) would come out of the clip below as a
         // clean eps and the fit would report success where the reference's isfinite assert fires
@@ -639,6 +645,9 @@ struct EmKernel {
         den = fmax(den, kTiny);  // mixture_model_utils.py:43-47
         const double rden = fast_rcp(den);
         const double sal = (!FINAL && a.saliency) ? a.saliency[(size_t)b * TS + tf + t] : 1.0;
+        // frame validity folded into the saliency, once per frame: the clipped posterior is finite
+        // (v_max / v_min drop a NaN), so gam * 0 is the 0 that a select per class used to pick
+        const double salm = ok[f] ? sal : 0.0;
         const double invp = inv + poison;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -660,7 +669,7 @@ struct EmKernel {
               }
             }
           } else {
-            double gs = ok[f] ? gam * sal : 0.0;
+            double gs = gam * salm;
             if (pub_kt && ok[f])
               __hip_atomic_store(pub_kt + (size_t)k * TS + tf + t, gs, __ATOMIC_RELAXED,
                                  __HIP_MEMORY_SCOPE_AGENT);

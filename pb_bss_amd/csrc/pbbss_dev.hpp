@@ -112,9 +112,21 @@ __device__ __forceinline__ double dpp_f64(double old, double src) {
   r.i[1] = __builtin_amdgcn_update_dpp(o.i[1], s.i[1], CTRL, 0xF, BANK, false);
   return r.d;
 }
+// result lane l = src[perm(l)] on the banks of BANK; the other banks are UNDEFINED.  For controls
+// under which every lane has a source (quad permutes, row mirrors, row rotations) and either all
+// banks or banks that the next dpp_f64 fills in: without an `old` operand tied to the result the
+// compiler needs no copy of a source that stays live (the butterflies paid two v_mov per exchange)
+template <int CTRL, int BANK = 0xF>
+__device__ __forceinline__ double dpp_mov_f64(double src) {
+  F64Bits s, r;
+  s.d = src;
+  r.i[0] = __builtin_amdgcn_mov_dpp(s.i[0], CTRL, 0xF, BANK, false);
+  r.i[1] = __builtin_amdgcn_mov_dpp(s.i[1], CTRL, 0xF, BANK, false);
+  return r.d;
+}
 template <int CTRL>
 __device__ __forceinline__ int dpp_i32(int src) {
-  return __builtin_amdgcn_update_dpp(src, src, CTRL, 0xF, 0xF, false);
+  return __builtin_amdgcn_mov_dpp(src, CTRL, 0xF, 0xF, false);
 }
 // v_permlane32_swap: a[32..63] <-> b[0..31];  v_permlane16_swap: odd rows of a <-> even rows of b
 __device__ __forceinline__ void swap32_f64(double& a, double& b) {
@@ -148,10 +160,10 @@ __device__ __forceinline__ void swap16_f64(double& a, double& b) {
 // quad permutes, 8- and 16-lane mirrors, then the two cross-row swaps.
 template <typename Op>
 __device__ __forceinline__ double wave_allreduce(double v, Op op) {
-  v = op(v, dpp_f64<kDppQuadXor1, 0xF>(v, v));
-  v = op(v, dpp_f64<kDppQuadXor2, 0xF>(v, v));
-  v = op(v, dpp_f64<kDppRowHalfMirror, 0xF>(v, v));
-  v = op(v, dpp_f64<kDppRowMirror, 0xF>(v, v));
+  v = op(v, dpp_mov_f64<kDppQuadXor1>(v));
+  v = op(v, dpp_mov_f64<kDppQuadXor2>(v));
+  v = op(v, dpp_mov_f64<kDppRowHalfMirror>(v));
+  v = op(v, dpp_mov_f64<kDppRowMirror>(v));
   double a = v, b = v;
   swap16_f64(a, b);
   v = op(a, b);
@@ -267,7 +279,7 @@ __device__ __forceinline__ void wave_reduce_scatter(double (&v)[N], int lane) {
 #pragma unroll
     for (int n = 0; n < H; ++n) {
       double lo = v[n], hi = v[n + H];
-      double recv = dpp_f64<kDppRowRor8, 0x3>(lo, lo);   // bit-clear lanes <- partner's lower value
+      double recv = dpp_mov_f64<kDppRowRor8, 0x3>(lo);   // bit-clear lanes <- partner's lower value
       recv = dpp_f64<kDppRowRor8, 0xC>(recv, hi);        // bit-set lanes   <- partner's upper value
       double keep = dpp_f64<kDppQuadIdent, 0xC>(lo, hi);  // own lower / own upper
       v[n] = keep + recv;
@@ -278,7 +290,7 @@ __device__ __forceinline__ void wave_reduce_scatter(double (&v)[N], int lane) {
 #pragma unroll
     for (int n = 0; n < H; ++n) {
       double lo = v[n], hi = v[n + H];
-      double recv = dpp_f64<kDppRowRor12, 0x5>(lo, lo);
+      double recv = dpp_mov_f64<kDppRowRor12, 0x5>(lo);
       recv = dpp_f64<kDppRowRor4, 0xA>(recv, hi);
       double keep = dpp_f64<kDppQuadIdent, 0xA>(lo, hi);
       v[n] = keep + recv;
@@ -286,9 +298,9 @@ __device__ __forceinline__ void wave_reduce_scatter(double (&v)[N], int lane) {
   }
   constexpr int R = N / 16;
 #pragma unroll
-  for (int n = 0; n < R; ++n) v[n] += dpp_f64<kDppQuadXor2, 0xF>(v[n], v[n]);
+  for (int n = 0; n < R; ++n) v[n] += dpp_mov_f64<kDppQuadXor2>(v[n]);
 #pragma unroll
-  for (int n = 0; n < R; ++n) v[n] += dpp_f64<kDppQuadXor1, 0xF>(v[n], v[n]);
+  for (int n = 0; n < R; ++n) v[n] += dpp_mov_f64<kDppQuadXor1>(v[n]);
 }
 // first original index owned by `lane` after wave_reduce_scatter<N>
 template <int N>
@@ -307,10 +319,10 @@ __device__ __forceinline__ double wave_sum_rows4(double v0, double v1, double v2
   double b = v1 + v3;  // lanes 0..31: v1, lanes 32..63: v3
   swap16_f64(a, b);
   double v = a + b;    // row 0: v0, row 1: v1, row 2: v2, row 3: v3
-  v += dpp_f64<kDppQuadXor1, 0xF>(v, v);
-  v += dpp_f64<kDppQuadXor2, 0xF>(v, v);
-  v += dpp_f64<kDppRowHalfMirror, 0xF>(v, v);
-  v += dpp_f64<kDppRowMirror, 0xF>(v, v);
+  v += dpp_mov_f64<kDppQuadXor1>(v);
+  v += dpp_mov_f64<kDppQuadXor2>(v);
+  v += dpp_mov_f64<kDppRowHalfMirror>(v);
+  v += dpp_mov_f64<kDppRowMirror>(v);
   return v;
 }
 // red[k] = sum over the 64 lanes of s[k], k < K (K <= 8), written by one lane per class
