@@ -102,6 +102,9 @@ int pbbss_destroy(pbbss_handle_t h);
 /*     distribution/complex_angular_central_gaussian.py:34-55                 */
 /*     (+ _unit_norm eps_style='where', distribution/utils.py:223-256)        */
 /* y (B,T,D) -> out (B,D,T), unit L2 norm over D; all-zero frames stay zero.  */
+/* Where the squared norm leaves float64 the result is the reference's: a     */
+/* frame whose squared norm underflows to 0 comes out as y / tiny, one whose   */
+/* squared norm overflows comes out as 0.                                      */
 /* is_c128: 0 = complex64 in/out, 1 = complex128 in/out.                      */
 /* ------------------------------------------------------------------------- */
 int pbbss_normalize_observation(pbbss_handle_t h, const void* y, int is_c128,

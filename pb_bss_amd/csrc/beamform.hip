@@ -450,8 +450,11 @@ __global__ void __launch_bounds__(256) normalize_kernel(const void* yv, int64_t 
       YS2 v = tile[tt * ld + d];
       n2 += (double)v.x * (double)v.x + (double)v.y * (double)v.y;
     }
-    // eps_style='where': zero norm -> divide by tiny -> stays 0 (utils.py:251)
-    double inv = (n2 > 0.0) ? 1.0 / sqrt(n2) : 0.0;
+    // eps_style='where': zero norm -> divide by tiny (utils.py:253).  An all-zero frame stays 0; a
+    // frame whose squared norm underflows to 0 comes out as y / tiny, as from the reference, whose
+    // np.linalg.norm squares the entries too (2^1022 = 1 / tiny, exact); an overflowing one has
+    // norm Inf there and comes out as 0; a NaN makes the whole frame NaN
+    double inv = (n2 == 0.0) ? 0x1p1022 : 1.0 / sqrt(n2);
     for (int d = 0; d < D; ++d) {
       YS2 v = tile[tt * ld + d];
       v.x = (YS)((double)v.x * inv);

@@ -180,14 +180,21 @@ def test_reference_channel_selection_stays_on_the_device_and_defers_its_assert()
 def test_select_reference_channel_kernel_against_the_host_selection():
     """pbbss_select_reference_channel (round 6): sums over the bins, NumPy's complex maximum with
     eps, first arg-max of the real part, column gather and the finiteness flag in one launch --
-    against `_select_reference_channel` (the host statement of beamformer.py:616-624) on both
-    problem layouts ((L, F) and (F, L) order of the matrices), with ties, denominators below eps,
-    a complex denominator whose real part equals eps, D up to 32 and a NaN."""
+    against beamformer.py:616-624 written out in NumPy here (no product code on the expected
+    side) on both problem layouts ((L, F) and (F, L) order of the matrices), with ties,
+    denominators below eps, a complex denominator whose real part equals eps, D up to 32 and a NaN.
+    Sensor counts that do not divide the 256 threads (S = 256 / D slots, leftover threads) with
+    fewer bins than slots (F = 1, 2) and more (F = 300)."""
     import torch
     from pb_bss_amd import _lib, engine
-    from pb_bss_amd.extraction.beamformer import _select_reference_channel
+
+    def expected_channel(num, den, eps):
+        snr = num.sum(0) / np.maximum(den.sum(0), eps)
+        return int(np.argmax(snr.real))
     rng = np.random.default_rng(11)
-    for L, F, D in ((3, 257, 6), (1, 5, 2), (4, 70, 32), (2, 1, 8)):
+    shapes = [(3, 257, 6), (1, 5, 2), (4, 70, 32), (2, 1, 8)]
+    shapes += [(2, F, D) for D in (1, 3, 5, 7, 29, 31) for F in (1, 2, 300)]
+    for L, F, D in shapes:
         mat = rng.standard_normal((L, F, D, D)) + 1j * rng.standard_normal((L, F, D, D))
         num = rng.uniform(0.5, 2.0, (L, F, D)) + 1e-3j * rng.standard_normal((L, F, D))
         den = rng.uniform(0.5, 2.0, (L, F, D)) + 1e-3j * rng.standard_normal((L, F, D))
@@ -206,7 +213,7 @@ def test_select_reference_channel_kernel_against_the_host_selection():
                     L * F, *a.shape[2:])) for a in (mat, num, den))
                 w, ref, ok = engine.select_reference_channel(m, n, d, L, F, eps, lead_stride=1,
                                                              bin_stride=L)
-            want = [_select_reference_channel(num[i], den[i], eps) for i in range(L)]
+            want = [expected_channel(num[i], den[i], eps) for i in range(L)]
             assert ref.tolist() == want, (L, F, D, order)
             assert ok.tolist() == [1] * L
             got = _lib.to_host(w)
