@@ -1299,6 +1299,40 @@ int pbbss_wpe_online(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, 
                      int32_t* out_status, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* XIV  Frame-recursive mask-driven MVDR beamformer (no counterpart in the     */
+/*      reference, which only applies time-dependent vectors:                  */
+/*      apply_online_beamforming_vector).  pb_bss_amd.extraction               */
+/*      recursive_mvdr_souden / OnlineMVDR.                                    */
+/* Frames are the strided (B, D, T) view of section XIII; the masks are (B, T) */
+/* contiguous, float32 or float64 (mask_is_f64), both >= 0.  Per problem and   */
+/* frame, in float64, in this order (s_t, v_t the target and noise mask):      */
+/*     Phi <- alpha Phi + s_t y_t y_t^H                                        */
+/*     n    = Psi y_t          den = alpha + v_t Re(y_t^H n)                   */
+/*     Psi <- (Psi - (v_t / den) n n^H) / alpha                                */
+/*     w_t  = Psi Phi[:, ref] / max(Re tr(Psi Phi), DBL_MIN)   x_t = w_t^H y_t  */
+/* Both updates compute the lower triangle with a real diagonal; the upper one */
+/* is the conjugate mirror.  State, read (lower triangle) and written (whole   */
+/* matrix, Hermitian to the bit) in place: target_psd Phi and noise_inv Psi    */
+/* (B, D, D) c128, frames_seen (B) int64.  A stream starts from Phi = 0,       */
+/* Psi = I / p0, frames_seen = 0; cutting it into calls of any lengths gives   */
+/* bit for bit what one call gives, and a batch what its problems give alone.  */
+/* out_x (B, T) contiguous, the type of y; out_w (T, B, D) c128 or null.       */
+/* out_status (B): PBBSS_ST_NONFINITE where den is not > 0 or den, Re tr or    */
+/* x_t is not finite: out_x and out_w of that problem are NaN from that frame  */
+/* on, as are its Phi and Psi; the other problems are unaffected.              */
+/* PBBSS_ERR_INVALID_ARG: null pointers (out_w may be null), B, D or T < 1,    */
+/*   alpha outside (0, 1], ref_channel outside [0, D).                         */
+/* PBBSS_ERR_UNSUPPORTED: D > 16, T beyond 2^29, B beyond 2^31 - 1.            */
+/* Nothing is written when an error code is returned.                          */
+/* ------------------------------------------------------------------------- */
+int pbbss_online_mvdr(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int D, int64_t T,
+                      int64_t stride_b, int64_t stride_d, int64_t stride_t,
+                      const void* target_mask, const void* noise_mask, int mask_is_f64,
+                      double alpha, int ref_channel, void* target_psd, void* noise_inv,
+                      int64_t* frames_seen, void* out_x, void* out_w, int32_t* out_status,
+                      void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Timing hook for bench.py: runs `fit` with HIP events recorded on `stream`   */
 /* around the EM kernel launch(es) only and returns the elapsed milliseconds   */
 /* of the most recent call (the roofline figure needs the kernel duration on   */

@@ -270,6 +270,8 @@ SIGNATURES = {
     'pbbss_wpe_apply_filter': [vp, vp, i32, i64, i32, i64, i64, i64, i64, vp, i32, i32, vp, vp],
     'pbbss_wpe_online': [vp, vp, i32, i64, i32, i64, i64, i64, i64, i32, i32, dbl, vp, vp, vp, vp,
         vp, vp, vp, vp],
+    'pbbss_online_mvdr': [vp, vp, i32, i64, i32, i64, i64, i64, i64, vp, vp, i32, dbl, i32, vp, vp,
+        vp, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 

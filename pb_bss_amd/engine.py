@@ -1097,6 +1097,46 @@ def wpe_online(y, taps, delay, alpha, power_estimate, inv_cov, filter_taps, hist
     return x, st
 
 
+# the frame-recursive MVDR beamformer: the shape plan of csrc/online_bf.hpp
+ONLINE_BF_MAX_D = 16   # sensors
+ONLINE_BF_TILE = 32    # frames staged, and output frames written, at a time
+
+
+def online_bf_served(D):
+    if D > ONLINE_BF_MAX_D:
+        raise NotImplementedError(f'recursive mvdr: D = {D} sensors, served up to '
+                                  f'ONLINE_BF_MAX_D = {ONLINE_BF_MAX_D}')
+
+
+def online_mvdr(y, target_mask, noise_mask, alpha, ref_channel, target_psd, noise_inv,
+                frames_seen, want_vector=False):
+    """pbbss_online_mvdr.  y: (B, D, T) view; the masks (B, T) f32 / f64 of one dtype; the state
+    -- target_psd, noise_inv (B, D, D) c128, frames_seen (B,) int64 -- is updated in place ->
+    (x (B, T) of the dtype of y, w (T, B, D) c128 or None, status (B,) int32)."""
+    t = _t()
+    y, head = _wpe_frames(y)
+    B, D, T = y.shape
+    online_bf_served(D)
+    assert 0.0 < alpha <= 1.0, alpha
+    assert 0 <= ref_channel < D, (ref_channel, D)
+    assert target_mask.shape == noise_mask.shape == (B, T) and \
+        target_mask.dtype == noise_mask.dtype and target_mask.dtype in (t.float32, t.float64), (
+            tuple(target_mask.shape), tuple(noise_mask.shape), target_mask.dtype, noise_mask.dtype,
+            tuple(y.shape))
+    assert target_psd.shape == noise_inv.shape == (B, D, D) and frames_seen.shape == (B,), (
+        tuple(target_psd.shape), tuple(noise_inv.shape), tuple(frames_seen.shape), tuple(y.shape))
+    assert target_psd.dtype == noise_inv.dtype == t.complex128 and frames_seen.dtype == t.int64, (
+        target_psd.dtype, noise_inv.dtype, frames_seen.dtype)
+    x = t.empty((B, T), dtype=y.dtype, device=y.device)
+    w = t.empty((T, B, D), dtype=t.complex128, device=y.device) if want_vector else None
+    st = t.empty((B,), dtype=t.int32, device=y.device)
+    _lib.launch('pbbss_online_mvdr', y.device, *head, target_mask.contiguous(),
+                noise_mask.contiguous(), target_mask.dtype == t.float64, alpha, ref_channel,
+                target_psd, noise_inv, frames_seen, x, w, st,
+                what=f'online_mvdr(B={B},D={D},T={T})')
+    return x, w, st
+
+
 def gmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, weight_mode=0,
             fixed_covariance=None, final_predict=False, want_log_pdf=False):
     """pbbss_gmm_fit (spherical covariances).  y (B,N,E) real, used as given (no row

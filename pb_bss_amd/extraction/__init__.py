@@ -24,6 +24,7 @@ from .beamformer import (
 )
 from .mask_module import *  # noqa: F401,F403  (extraction/__init__.py:1)
 from .mask_module import __all__ as _mask_names
+from .online_beamformer import OnlineBeamformerState, OnlineMVDR, recursive_mvdr_souden
 from .beamformer_wrapper import get_bf_vector
 from .beamformer_wrapper import get_bf_vector as get_single_source_bf_vector  # extraction/__init__.py:4
 
@@ -37,4 +38,5 @@ __all__ = [
     'zero_degree_normalization', 'phase_correction', 'condition_covariance',
     'apply_online_beamforming_vector', 'get_single_source_bf_vector',
 ]
+__all__ += ['recursive_mvdr_souden', 'OnlineMVDR', 'OnlineBeamformerState']
 __all__ += _mask_names
