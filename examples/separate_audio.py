@@ -6,6 +6,14 @@
 
     python examples/separate_audio.py --seconds 8 --sensors 6 --sources 2 [--wpe [recursive]]
 
+With --online the model is fitted and aligned on a first block only and the rest runs block by
+block through the frame-recursive stages, the state of all three on the device:
+
+    first block --cACGMM EM--> masks --DHTV alignment--> one M-step --> CACGMM (aligned classes)
+    every block [--OnlineWPE-->] --OnlineCACGMM--> masks (F, K, Tb) --OnlineMVDR per class--> (F, Tb)
+
+    python examples/separate_audio.py --online [--first-block 2] [--block-frames 16] [--wpe recursive]
+
 Synthetic scene: `sources` on/off-modulated noise bursts through random short room filters
 plus sensor noise.  Prints the time per stage and, per source, the correlation of the best
 matching output with the source image at the reference sensor before and after separation.
@@ -58,7 +66,17 @@ def main():
                          "(the default of a bare --wpe; pb_bss_amd.transform.wpe, 3 iterations) "
                          "or 'recursive' (transform.recursive_wpe: one filter update per frame, "
                          "alpha 0.9999)")
+    ap.add_argument('--online', action='store_true',
+                    help="fit and align on the first block only, then OnlineWPE (with --wpe "
+                         "recursive) -> OnlineCACGMM -> OnlineMVDR over blocks of frames")
+    ap.add_argument('--first-block', type=float, default=2.0,
+                    help='--online: seconds of the block the offline model is fitted on')
+    ap.add_argument('--block-frames', type=int, default=16, help='--online: frames per block')
+    ap.add_argument('--alpha', type=float, default=0.99,
+                    help='--online: forgetting factor of the mask estimator and the beamformer')
     args = ap.parse_args()
+    if args.online and args.wpe == 'offline':
+        ap.error("--online streams: use --wpe recursive")
     import torch
     from pb_bss_amd import initializer
     from pb_bss_amd.distribution import CACGMMTrainer
@@ -118,8 +136,59 @@ def main():
         mark('istft')
         return y, marks
 
+    def run_online(x):
+        from pb_bss_amd.distribution import OnlineCACGMM
+        from pb_bss_amd.extraction import OnlineMVDR
+        from pb_bss_amd.transform import OnlineWPE
+        np.random.seed(0)
+        marks = [('start', time.perf_counter())]
+
+        def mark(name):
+            torch.cuda.synchronize()
+            marks.append((name, time.perf_counter()))
+
+        Y = stft(x, args.size, args.shift, layout='f t d', dtype=np.complex64)   # (F, T, D)
+        mark('stft')
+        F, T, D = Y.shape
+        Tb = args.block_frames
+        T0 = max(1, int(args.first_block * args.rate / args.shift))
+        T0 = min(T, -(-T0 // Tb) * Tb)                                       # whole blocks
+        dereverb = OnlineWPE(channel=D, frequency_bins=F) if args.wpe else None
+        head = dereverb.step_block(Y[:, :T0].contiguous()) if dereverb else Y[:, :T0].contiguous()
+        masks = CACGMMTrainer().fit_predict(head, iterations=args.iterations, num_classes=K)
+        solver = DHTVPermutationAlignment.from_stft_size(args.size)
+        kft = solver(masks.transpose(0, 1).contiguous())                     # (K, F, T0), aligned
+        # the model of the aligned classes: one M-step from the aligned masks
+        model = CACGMMTrainer().fit(head, initialization=kft.transpose(0, 1).contiguous(),
+                                    iterations=1)
+        mark(f'first block ({T0} frames): cACGMM x{args.iterations} + DHTV + M-step')
+        estimator = OnlineCACGMM(model, args.alpha)
+        beamformers = [OnlineMVDR(D, F, args.alpha, 0) for _ in range(K)]
+        out = []
+        for t0 in range(0, T, Tb):
+            t1 = min(T, t0 + Tb)
+            if t1 <= T0:
+                block = head[:, t0:t1].contiguous()                          # dereverberated above
+            else:
+                block = Y[:, t0:t1].contiguous()
+                block = dereverb.step_block(block) if dereverb else block
+            aff = estimator.step_block(block)                                # (F, K, Tb), a-priori
+            out.append(torch.stack([bf.step_block(block, aff[:, k], 1.0 - aff[:, k]) * aff[:, k]
+                                    for k, bf in enumerate(beamformers)]))   # (K, F, Tb)
+        S = torch.cat(out, dim=2).transpose(1, 2).contiguous()               # (K, T, F)
+        flagged = int((estimator.status != 0).sum())
+        mark(f'{len(out)} blocks of {Tb}: '
+             f'{"OnlineWPE + " if dereverb else ""}OnlineCACGMM + {K} OnlineMVDR'
+             f'{f" ({flagged} bins flagged)" if flagged else ""}')
+        y = istft(S, args.size, args.shift)[..., :n]                         # (K, samples)
+        mark('istft')
+        return y, marks
+
+    if args.online:
+        run = run_online
     x = torch.from_numpy(mix).cuda()
-    run(x[:, :args.rate])                                                    # warm-up
+    run(x[:, :max(args.rate, int(1.5 * args.first_block * args.rate)) if args.online
+          else args.rate])                                                   # warm-up
     torch.cuda.synchronize()
     y, marks = run(x)
     est = y.cpu().numpy()

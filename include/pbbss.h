@@ -1333,6 +1333,45 @@ int pbbss_online_mvdr(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B,
                       void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* XV  Frame-recursive cACGMM mask estimator (no counterpart in the reference, */
+/*     which only has the batch EM).  pb_bss_amd.distribution                  */
+/*     recursive_cacgmm / OnlineCACGMM.                                        */
+/* Frames are the strided (B, D, T) view of section XIII.  Per problem with K  */
+/* classes and per frame y, in float64, in this order:                         */
+/*     nu = sqrt(sum_d |y_d|^2); nu == 0: gamma_k = pi_k, q_k = 0, the state   */
+/*          is not touched; else z = y / nu                                    */
+/*     n_k = P_k z        q_k = Re(z^H n_k)                                    */
+/*     gamma = softmax_k(log pi_k - L_k - D log q_k), clipped to               */
+/*          [eps, 1 - eps] without renormalisation if affiliation_eps > 0      */
+/*     old = alpha Lambda_k   new = old + gamma_k   den = old + D gamma_k      */
+/*     P_k <- (P_k - ((D gamma_k / (q_k den)) n_k) n_k^H) (new / old)          */
+/*     L_k <- L_k + D log(old / new) + log(den / old)      Lambda_k <- new     */
+/*     pi_k = Lambda_k / sum_j Lambda_j   (if update_weight)                   */
+/* out_affiliation holds the gamma of a frame BEFORE that frame's update.  The */
+/* update computes the lower triangle with a real diagonal; the upper one is   */
+/* the conjugate mirror.  State, read and written in place: precision P        */
+/* (B, K, D, D) c128 (the lower triangle is read, the whole matrix written,    */
+/* Hermitian to the bit), log_determinant L, count Lambda > 0, weight pi > 0   */
+/* (B, K) float64, frames_seen (B) int64.  Cutting a stream into calls of any  */
+/* lengths gives bit for bit what one call gives, and a batch what its         */
+/* problems give alone.  out_affiliation, out_quadratic_form (or null):        */
+/* (B, K, T) float64.  out_status (B): PBBSS_ST_NONFINITE where a q_k or an    */
+/* old is not > 0 or a q, gamma, L or Lambda is not finite: both outputs of    */
+/* that problem are NaN from that frame on, as are its P, L, Lambda and pi;    */
+/* the other problems are unaffected.                                          */
+/* PBBSS_ERR_INVALID_ARG: null pointers (out_quadratic_form may be null), B or */
+/*   T < 1, D or K < 2, alpha outside (0, 1], affiliation_eps outside [0, .5). */
+/* PBBSS_ERR_UNSUPPORTED: D > 16, K > 8, T beyond 2^29, B beyond 2^31 - 1.     */
+/* Nothing is written when an error code is returned.                          */
+/* ------------------------------------------------------------------------- */
+int pbbss_online_cacgmm(pbbss_handle_t h, const void* y, int y_is_c128, int64_t B, int D, int K,
+                        int64_t T, int64_t stride_b, int64_t stride_d, int64_t stride_t,
+                        double alpha, double affiliation_eps, int update_weight, void* precision,
+                        double* log_determinant, double* count, double* weight,
+                        int64_t* frames_seen, double* out_affiliation,
+                        double* out_quadratic_form, int32_t* out_status, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Timing hook for bench.py: runs `fit` with HIP events recorded on `stream`   */
 /* around the EM kernel launch(es) only and returns the elapsed milliseconds   */
 /* of the most recent call (the roofline figure needs the kernel duration on   */

@@ -272,6 +272,8 @@ SIGNATURES = {
         vp, vp, vp, vp],
     'pbbss_online_mvdr': [vp, vp, i32, i64, i32, i64, i64, i64, i64, vp, vp, i32, dbl, i32, vp, vp,
         vp, vp, vp, vp, vp],
+    'pbbss_online_cacgmm': [vp, vp, i32, i64, i32, i32, i64, i64, i64, i64, dbl, dbl, i32, vp, vp,
+        vp, vp, vp, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -21,6 +21,7 @@ from .gaussian import DiagonalGaussian, Gaussian, SphericalGaussian, GaussianTra
 from .gmm import GMM, GMMTrainer, BinaryGMM, BinaryGMMTrainer
 from .gcacgmm import GCACGMM, GCACGMMTrainer
 from .vmfcacgmm import VMFCACGMM, VMFCACGMMTrainer
+from .online_cacgmm import OnlineCACGMM, OnlineCACGMMState, recursive_cacgmm
 
 __all__ = [
     'CACGMM', 'CACGMMTrainer', 'CWMM', 'CWMMTrainer', 'CBMM', 'CBMMTrainer',
@@ -33,4 +34,5 @@ __all__ = [
     'ComplexAngularCentralGaussian', 'ComplexAngularCentralGaussianTrainer',
     'ComplexCircularSymmetricGaussian', 'ComplexCircularSymmetricGaussianTrainer',
     'normalize_observation', 'sample_cacgmm', 'sample_complex_angular_central_gaussian',
+    'recursive_cacgmm', 'OnlineCACGMM', 'OnlineCACGMMState',
 ]

@@ -1137,6 +1137,52 @@ def online_mvdr(y, target_mask, noise_mask, alpha, ref_channel, target_psd, nois
     return x, w, st
 
 
+# the frame-recursive cACGMM mask estimator: the shape plan of csrc/online_cacgmm.hpp
+ONLINE_CACGMM_MAX_D = 16   # sensors
+ONLINE_CACGMM_MAX_K = 8    # classes
+ONLINE_CACGMM_TILE = 32    # frames staged, and output frames written, at a time
+
+
+def online_cacgmm_served(D, K):
+    if D < 2 or K < 2:
+        raise ValueError(f'recursive cacgmm needs D >= 2 sensors and K >= 2 classes, got D = {D}, '
+                         f'K = {K}')
+    if D > ONLINE_CACGMM_MAX_D:
+        raise NotImplementedError(f'recursive cacgmm: D = {D} sensors, served up to '
+                                  f'ONLINE_CACGMM_MAX_D = {ONLINE_CACGMM_MAX_D}')
+    if K > ONLINE_CACGMM_MAX_K:
+        raise NotImplementedError(f'recursive cacgmm: K = {K} classes, served up to '
+                                  f'ONLINE_CACGMM_MAX_K = {ONLINE_CACGMM_MAX_K}')
+
+
+def online_cacgmm(y, alpha, affiliation_eps, update_weight, precision, log_determinant, count,
+                  weight, frames_seen, want_q=False):
+    """pbbss_online_cacgmm.  y: (B, D, T) view; the state -- precision (B, K, D, D) c128,
+    log_determinant, count, weight (B, K) f64, frames_seen (B,) int64 -- is updated in place ->
+    (affiliation (B, K, T) f64, quadratic_form (B, K, T) f64 or None, status (B,) int32)."""
+    t = _t()
+    y, head = _wpe_frames(y)
+    B, D, T = y.shape
+    K = precision.shape[1] if precision.ndim == 4 else 0
+    online_cacgmm_served(D, K)
+    assert 0.0 < alpha <= 1.0, alpha
+    assert 0.0 <= affiliation_eps < 0.5, affiliation_eps
+    assert precision.shape == (B, K, D, D) and frames_seen.shape == (B,) and \
+        log_determinant.shape == count.shape == weight.shape == (B, K), (
+            tuple(precision.shape), tuple(log_determinant.shape), tuple(count.shape),
+            tuple(weight.shape), tuple(frames_seen.shape), tuple(y.shape))
+    assert precision.dtype == t.complex128 and frames_seen.dtype == t.int64 and \
+        log_determinant.dtype == count.dtype == weight.dtype == t.float64, (
+            precision.dtype, log_determinant.dtype, count.dtype, weight.dtype, frames_seen.dtype)
+    aff = t.empty((B, K, T), dtype=t.float64, device=y.device)
+    q = t.empty((B, K, T), dtype=t.float64, device=y.device) if want_q else None
+    st = t.empty((B,), dtype=t.int32, device=y.device)
+    _lib.launch('pbbss_online_cacgmm', y.device, head[0], head[1], B, D, K, *head[4:], alpha,
+                affiliation_eps, bool(update_weight), precision, log_determinant, count, weight,
+                frames_seen, aff, q, st, what=f'online_cacgmm(B={B},D={D},K={K},T={T})')
+    return aff, q, st
+
+
 def gmm_fit(y, K, *, gamma0=None, model=None, iterations=100, saliency=None, weight_mode=0,
             fixed_covariance=None, final_predict=False, want_log_pdf=False):
     """pbbss_gmm_fit (spherical covariances).  y (B,N,E) real, used as given (no row
