@@ -2022,6 +2022,9 @@ struct EmKernel {
     }
     __syncthreads();
     for (int it = 0; it < a.iterations; ++it) {
+      // The members keep their roles on their waves (no em_role here): with the members' roles
+      // moving over the SIMDs like those of run() the headline step came out 1.5 % SLOWER than
+      // with pinned ones (profiles/r12_a_wave_roles.txt, section 3)
       if (it > 0 || model_in) {
         // windows are <= 256 frames (one E pass): waves that own no frame skip the phase
         if ((wave << 6) < a.T) {
@@ -2297,6 +2300,8 @@ struct EmKernel {
     if (kt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int it = 0; it < a.iterations; ++it) {
+      // (roles stay on their waves here: em_role made no difference beyond the run-to-run spread
+      // of this kernel, profiles/r12_a_wave_roles.txt section 3)
       if (it > 0 || model_in) {
         double* pub = kt ? a.gaff + ((size_t)(it & 1) * a.B + b) * K * TS : nullptr;
         if (kt) {
@@ -2396,13 +2401,17 @@ struct EmKernel {
       __syncthreads();
       PBBSS_TICK(0)
       for (int it = 0; it < a.iterations; ++it) {
+        // this iteration's role of the wave (em_role, pbbss_dev.hpp): E chunks, M entries and
+        // classes to factor go by vw / vtid, everything outside the loop by the physical indices
+        const int vw = em_role(wave, it);
+        const int vtid = (vw << 6) | lane;
         if (it > 0 || model_in) {
-          phase_e<false, false, false, PBBSS_E_PAIR != 0>(a, L, b, tid, wave, lane, a.aff_eps);
+          phase_e<false, false, false, PBBSS_E_PAIR != 0>(a, L, b, vtid, vw, lane, a.aff_eps);
           PBBSS_TICK(1)
           __syncthreads();
           PBBSS_TICK(2)
         }
-        switch (wave) {
+        switch (vw) {
           case 0: phase_m<0>(a, L, lane); break;
           case 1: phase_m<1>(a, L, lane); break;
           case 2: phase_m<2>(a, L, lane); break;
@@ -2412,7 +2421,7 @@ struct EmKernel {
         __syncthreads();
         PBBSS_TICK(4)
         const bool last = (it == a.iterations - 1);
-        for (int k = wave; k < K; k += kEmWaves) factor_class(a, L, b, k, lane, last);
+        for (int k = vw; k < K; k += kEmWaves) factor_class(a, L, b, k, lane, last);
         PBBSS_TICK(5)
         __syncthreads();
         PBBSS_TICK(6)

@@ -656,6 +656,7 @@ struct EmKernel32 {
     }
     __syncthreads();
     for (int it = 0; it < a.iterations; ++it) {
+      // (the members keep their roles on their waves: see run_split of cacgmm_em.hpp)
       if (it > 0 || model_in) {
         if ((wave << 6) < a.T) {  // windows are <= 256 frames: one E pass
           phase_e<false>(a, L, b, tid, wave, lane, (float)a.aff_eps, tf);
@@ -746,13 +747,16 @@ struct EmKernel32 {
       __syncthreads();
       PBBSS_TICK32(0)
       for (int it = 0; it < a.iterations; ++it) {
+        // this iteration's role of the wave (em_role, pbbss_dev.hpp), as in EmKernel::run
+        const int vw = em_role(wave, it);
+        const int vtid = (vw << 6) | lane;
         if (it > 0 || model_in) {
-          phase_e<false>(a, L, b, tid, wave, lane, (float)a.aff_eps);
+          phase_e<false>(a, L, b, vtid, vw, lane, (float)a.aff_eps);
           PBBSS_TICK32(1)
           __syncthreads();
           PBBSS_TICK32(2)
         }
-        phase_m_dispatch(a, L, wave, lane);
+        phase_m_dispatch(a, L, vw, lane);
         PBBSS_TICK32(3)
         __syncthreads();
         PBBSS_TICK32(4)
@@ -760,7 +764,7 @@ struct EmKernel32 {
         // (factor_class raises the priority itself only where split_groups == 0; this launch
         // carries the group count for its in-grid members, so the hosts do it here)
         __builtin_amdgcn_s_setprio(3);
-        for (int k = wave; k < K; k += kEmWaves) {
+        for (int k = vw; k < K; k += kEmWaves) {
           Base::factor_class(a, L.b, b, k, lane, last);
           publish_class(L, k, lane);  // same wave wrote apack of class k: wave-ordered LDS
         }

@@ -23,6 +23,27 @@ constexpr int kWave = 64;       // CDNA wavefront width
 constexpr int kEmThreads = 256; // EM workgroup: one wave per SIMD of a CU
 constexpr int kEmWaves = kEmThreads / kWave;
 
+// Role of physical wave `wave` in iteration `it` of a persistent EM loop.  The roles of an
+// iteration (E chunks w, w + 4; the entries of phase_m<w>; classes w, w + 4 of the factorisation)
+// do not carry the same number of instructions -- at K = 3 one role factors nothing -- and a wave
+// stays on its SIMD for the whole fit: the roles therefore move on by one wave per iteration, so
+// that every SIMD carries every role in turn.  Everything the roles exchange is addressed by role
+// slot and every phase ends in a barrier, so the order of every sum is the same as with pinned
+// roles (-DPBBSS_EM_ROTATE=0).  Wave-uniform; iteration 0 keeps role == wave.  Used by the full
+// workgroups of the float64 and the packed-FP32 kernel (1 .. 3 % of the headline step); the
+// member workgroups of a remainder bin and the shared-weight kernel keep their roles pinned
+// (slower / no measurable difference: profiles/r12_a_wave_roles.txt).
+#ifndef PBBSS_EM_ROTATE
+#define PBBSS_EM_ROTATE 1
+#endif
+__device__ __forceinline__ int em_role(int wave, int it) {
+#if PBBSS_EM_ROTATE
+  return (wave + it) & (kEmWaves - 1);
+#else
+  return wave;
+#endif
+}
+
 // ---- compile-time loop: body(std::integral_constant<int, I>{}) for I in [B, E)
 template <int B, int E, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
