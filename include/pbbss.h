@@ -72,7 +72,11 @@ const char* pbbss_error_string(int code);
  * each call and restores the caller's selection; all
  * pointers are device pointers unless stated otherwise; calls only enqueue work (no host
  * synchronisation) unless stated otherwise; one handle must not be used from two host
- * threads at the same time (create one per thread, as pb_bss_amd/_lib.py does).  PBBSS_DEBUG
+ * threads at the same time (create one per thread, as pb_bss_amd/_lib.py does).  A handle
+ * serves ONE stream at a time: consecutive calls carve their workspaces from the same device
+ * memory of the handle, so before the handle is used on another stream, that stream must be
+ * ordered behind the work enqueued through the handle so far (an event recorded on the old
+ * stream and hipStreamWaitEvent on the new one; pb_bss_amd/_lib.py: launch does this).  PBBSS_DEBUG
  * in the environment makes pbbss_create report failing HIP calls on stderr. */
 int pbbss_create(pbbss_handle_t* out, int device_id);
 /* Shape range.  2 <= D <= 8 sensors: the fused kernels (one wavefront per D x D matrix; the

@@ -359,9 +359,19 @@ def handle(device_index=None):
         return h
 
 
-def stream_ptr(device_index=None):
-    t = torch()
-    return ctypes.c_void_p(t.cuda.current_stream(device_index).cuda_stream)
+def current_stream(device_index=None):
+    return torch().cuda.current_stream(device_index)
+
+
+def is_capturing():
+    return torch().cuda.is_current_stream_capturing()
+
+
+def stream_ptr(device_index=None, stream=None):
+    """hipStream_t of `stream`, by default of the current torch stream of the device"""
+    if stream is None:
+        stream = current_stream(device_index)
+    return ctypes.c_void_p(stream.cuda_stream)
 
 
 _CTYPES_POINTERS = (ctypes._SimpleCData, ctypes.Array, bytes)  # c_void_p, arrays, string buffers
@@ -407,16 +417,44 @@ def _marshal(name, converters, expected, args):
     return [c(a) for c, a in zip(converters, args)]
 
 
+# handle key -> the torch stream of the last launch through that handle.  Consecutive calls carve
+# their workspaces from the same slabs of the handle, so a call on another stream has to be
+# ordered behind what the handle has enqueued so far (include/pbbss.h: one stream at a time).
+# One entry per (device, host thread), as _handles, and as long-lived: an entry that outlives its
+# handle, or is inherited with a recycled thread ident, costs the next launch one wait and no more.
+_last_stream = {}
+
+
+def _ordered_stream(index):
+    """The current stream of the device, ordered behind the stream of the handle's previous launch
+    where that was another one.  The same-stream path is one comparison and no runtime call.
+    During a graph capture nothing is ordered or remembered: torch.cuda.graph has synchronised
+    the device before the capture began, and the capture's private stream is gone after it.  (The
+    capture query is torch's, about the current stream of the CURRENT device: a caller that
+    captures on one device while launching on another is not covered.)"""
+    stream = current_stream(index)
+    key = (stream.device_index, threading.get_ident())
+    last = _last_stream.get(key)
+    # the handles of the two streams, not the objects: torch.Stream answers False to `!= None`
+    if (last is None or last.cuda_stream != stream.cuda_stream) and not is_capturing():
+        if last is not None:
+            stream.wait_stream(last)
+        _last_stream[key] = stream
+    return stream
+
+
 def launch(name, device, *args, what=None, accept=()):
     """Call an export whose first parameter is the handle and whose last is the stream: this
     thread's handle of `device` (a torch.device or an index), `args` marshalled slot by slot from
     SIGNATURES[name] (pointer slots: None, a contiguous device tensor or a ctypes object; option
     structs by reference; scalars through int() / float()), the current torch stream of the device
-    read now.  Raises through check(rc, what or name) unless rc is in `accept`; returns rc."""
+    read now and ordered behind the stream of the handle's previous launch.  Raises through
+    check(rc, what or name) unless rc is in `accept`; returns rc."""
     index = _index(device)
     converters = _CONVERTERS[name]
     argv = _marshal(name, converters, len(converters) - 1, args)
-    rc = getattr(load(), name)(handle(index), *argv, stream_ptr(index))
+    stream = _ordered_stream(index)
+    rc = getattr(load(), name)(handle(index), *argv, stream_ptr(index, stream))
     if rc != OK and rc not in accept:
         check(rc, what or name)
     return rc

@@ -52,6 +52,29 @@ class StubLibrary:
         return export
 
 
+class FakeStream:
+    """stand-in of a torch stream: records the streams it was made to wait for, and how many
+    exports had been called by then"""
+
+    def __init__(self, lib, cuda_stream, device_index=0):
+        self.lib, self.cuda_stream, self.device_index = lib, cuda_stream, device_index
+        self.waits = []
+
+    def wait_stream(self, other):
+        self.waits.append((other, len(self.lib.calls)))
+
+    # torch.Stream compares by stream id and device, and answers False to EVERY comparison with
+    # None, `!=` included: an ordering that asks `last != stream` never starts
+    def __eq__(self, other):
+        return other is not None and (self.cuda_stream, self.device_index) == (
+            other.cuda_stream, other.device_index)
+
+    def __ne__(self, other):
+        return other is not None and not self == other
+
+    __hash__ = object.__hash__
+
+
 @pytest.fixture
 def stub(monkeypatch):
     from pb_bss_amd import _lib
@@ -59,6 +82,13 @@ def stub(monkeypatch):
     lib.handle = ctypes.c_void_p(0x1000)
     lib.stream = ctypes.c_void_p(0x2000)
     lib.devices = []
+    lib.current = FakeStream(lib, 0x2000)   # what torch.cuda.current_stream() would give
+    lib.capturing = False
+    lib.capture_queries = 0
+
+    def is_capturing():
+        lib.capture_queries += 1
+        return lib.capturing
 
     def handle(device_index=None):
         lib.devices.append(device_index)
@@ -66,7 +96,10 @@ def stub(monkeypatch):
 
     monkeypatch.setattr(_lib, 'load', lambda: lib)
     monkeypatch.setattr(_lib, 'handle', handle)
-    monkeypatch.setattr(_lib, 'stream_ptr', lambda device_index=None: lib.stream)
+    monkeypatch.setattr(_lib, 'stream_ptr', lambda device_index=None, stream=None: lib.stream)
+    monkeypatch.setattr(_lib, 'current_stream', lambda device_index=None: lib.current)
+    monkeypatch.setattr(_lib, 'is_capturing', is_capturing)
+    monkeypatch.setattr(_lib, '_last_stream', {})
     return lib
 
 
@@ -174,6 +207,69 @@ def test_launch_marshalling(stub):
     assert _lib.view_ptr(FakeTensor(0x900, contiguous=False)).value == 0x900
     with pytest.raises(AssertionError):
         _lib.view_ptr(FakeTensor(0x900, cuda=False))
+
+
+def test_launch_orders_a_new_stream_behind_the_previous_one(stub):
+    """Consecutive calls on one handle share its workspaces: `launch` remembers, per handle key,
+    the stream of the last launch and makes another stream wait for it before the export runs."""
+    import threading
+    from pb_bss_amd import _lib
+    me = threading.get_ident()
+
+    def call(device=0):                         # any export with a stream will do
+        _lib.launch('pbbss_heev_batched', device, None, 1, 2, None, None, None)
+
+    a, b, c = stub.current, FakeStream(stub, 0x2100), FakeStream(stub, 0x2200)
+    call()                                     # the first launch of the key: nothing to wait for
+    assert a.waits == [] and _lib._last_stream == {(0, me): a}
+    queries = stub.capture_queries
+    call()
+    call()                                     # same stream: no wait, no runtime query at all
+    assert a.waits == [] and stub.capture_queries == queries and len(stub.calls) == 3
+    stub.current = b                            # switch: one wait, before the export is called
+    call()
+    assert b.waits == [(a, 3)] and a.waits == [] and len(stub.calls) == 4
+    assert _lib._last_stream[(0, me)] is b
+    call()
+    assert b.waits == [(a, 3)]
+    stub.current = a                            # switch back: again one wait
+    call()
+    assert a.waits == [(b, 5)] and b.waits == [(a, 3)]
+    call()
+    assert a.waits == [(b, 5)]
+    # a capture in progress: nothing is ordered, the remembered stream stays
+    stub.current, stub.capturing = c, True
+    call()
+    call()
+    assert c.waits == [] and _lib._last_stream[(0, me)] is a and len(stub.calls) == 9
+    stub.current, stub.capturing = a, False
+    call()                                     # back on the remembered stream: still no wait
+    assert a.waits == [(b, 5)]
+    # the remembered stream is kept per handle key: another device starts from nothing ...
+    other = FakeStream(stub, 0x2300, device_index=1)
+    stub.current = other
+    call(1)
+    assert other.waits == [] and _lib._last_stream == {(0, me): a, (1, me): other}
+    # ... another thread too, and neither disturbs the first key
+    seen = {}
+
+    def worker():
+        stub.current = b
+        call()
+        seen['key'] = (0, threading.get_ident())
+    t = threading.Thread(target=worker)
+    t.start()
+    t.join()
+    assert b.waits == [(a, 3)] and _lib._last_stream[(0, me)] is a
+    # (a finished thread's ident may be handed out again: only the entry itself is checked)
+    assert _lib._last_stream[seen['key']] is b
+    stub.current = a
+    call()
+    assert a.waits == [(b, 5)]
+    # a device given as None is keyed by the device of the current stream
+    stub.current = b
+    _lib.launch('pbbss_heev_batched', None, None, 1, 2, None, None, None)
+    assert b.waits[-1][0] is a and _lib._last_stream[(0, me)] is b
 
 
 def _package_sources():
