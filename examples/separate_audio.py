@@ -6,11 +6,14 @@
 
     python examples/separate_audio.py --seconds 8 --sensors 6 --sources 2 [--wpe [recursive]]
 
-With --online the model is fitted and aligned on a first block only and the rest runs block by
-block through the frame-recursive stages, the state of all three on the device:
+With --online the model is fitted and aligned on a first block only and the rest runs sample block
+by sample block (block-frames * shift samples) through the streaming stages, the state of all of
+them on the device; the audio is bit for bit what the offline stft / istft around the same stages
+give:
 
-    first block --cACGMM EM--> masks --DHTV alignment--> one M-step --> CACGMM (aligned classes)
-    every block [--OnlineWPE-->] --OnlineCACGMM--> masks (F, K, Tb) --OnlineMVDR per class--> (F, Tb)
+    first block --OnlineSTFT--> --cACGMM EM--> masks --DHTV alignment--> one M-step --> CACGMM
+    every block --OnlineSTFT--> [--OnlineWPE-->] --OnlineCACGMM--> masks (F, K, Tb)
+                --OnlineMVDR per class--> (K, F, Tb) --OnlineISTFT('f t')--> audio (K, block)
 
     python examples/separate_audio.py --online [--first-block 2] [--block-frames 16] [--wpe recursive]
 
@@ -67,13 +70,17 @@ def main():
                          "or 'recursive' (transform.recursive_wpe: one filter update per frame, "
                          "alpha 0.9999)")
     ap.add_argument('--online', action='store_true',
-                    help="fit and align on the first block only, then OnlineWPE (with --wpe "
-                         "recursive) -> OnlineCACGMM -> OnlineMVDR over blocks of frames")
+                    help="fit and align on the first block only, then OnlineSTFT -> OnlineWPE (with "
+                         "--wpe recursive) -> OnlineCACGMM -> OnlineMVDR -> OnlineISTFT over blocks "
+                         "of block-frames * shift samples")
     ap.add_argument('--first-block', type=float, default=2.0,
                     help='--online: seconds of the block the offline model is fitted on')
-    ap.add_argument('--block-frames', type=int, default=16, help='--online: frames per block')
+    ap.add_argument('--block-frames', type=int, default=16,
+                    help='--online: frames per block (the block is block-frames * shift samples)')
     ap.add_argument('--alpha', type=float, default=0.99,
                     help='--online: forgetting factor of the mask estimator and the beamformer')
+    ap.add_argument('--save', metavar='FILE.npy',
+                    help='write the separated audio (classes, samples) float64 to this file')
     args = ap.parse_args()
     if args.online and args.wpe == 'offline':
         ap.error("--online streams: use --wpe recursive")
@@ -136,10 +143,12 @@ def main():
         mark('istft')
         return y, marks
 
+    notes = []
+
     def run_online(x):
         from pb_bss_amd.distribution import OnlineCACGMM
         from pb_bss_amd.extraction import OnlineMVDR
-        from pb_bss_amd.transform import OnlineWPE
+        from pb_bss_amd.transform import OnlineISTFT, OnlineSTFT, OnlineWPE
         np.random.seed(0)
         marks = [('start', time.perf_counter())]
 
@@ -147,41 +156,51 @@ def main():
             torch.cuda.synchronize()
             marks.append((name, time.perf_counter()))
 
-        Y = stft(x, args.size, args.shift, layout='f t d', dtype=np.complex64)   # (F, T, D)
-        mark('stft')
-        F, T, D = Y.shape
-        Tb = args.block_frames
+        D, F, Tb = x.shape[0], args.size // 2 + 1, args.block_frames
+        block_samples = Tb * args.shift
+        analysis = OnlineSTFT(D, args.size, args.shift, dtype=np.complex64)  # -> (F, m, D)
+        synthesis = OnlineISTFT(args.size, args.shift, layout='f t')         # (K, F, m) ->
         T0 = max(1, int(args.first_block * args.rate / args.shift))
-        T0 = min(T, -(-T0 // Tb) * Tb)                                       # whole blocks
+        T0 = -(-T0 // Tb) * Tb                                               # whole blocks
+        n0 = min(x.shape[1], T0 * args.shift)
+        head = analysis.step_block(x[:, :n0])                                # (F, T0, D)
         dereverb = OnlineWPE(channel=D, frequency_bins=F) if args.wpe else None
-        head = dereverb.step_block(Y[:, :T0].contiguous()) if dereverb else Y[:, :T0].contiguous()
+        head = dereverb.step_block(head) if dereverb else head
         masks = CACGMMTrainer().fit_predict(head, iterations=args.iterations, num_classes=K)
         solver = DHTVPermutationAlignment.from_stft_size(args.size)
         kft = solver(masks.transpose(0, 1).contiguous())                     # (K, F, T0), aligned
         # the model of the aligned classes: one M-step from the aligned masks
         model = CACGMMTrainer().fit(head, initialization=kft.transpose(0, 1).contiguous(),
                                     iterations=1)
-        mark(f'first block ({T0} frames): cACGMM x{args.iterations} + DHTV + M-step')
+        mark(f'first block ({head.shape[1]} frames): OnlineSTFT + cACGMM x{args.iterations} + '
+             'DHTV + M-step')
         estimator = OnlineCACGMM(model, args.alpha)
         beamformers = [OnlineMVDR(D, F, args.alpha, 0) for _ in range(K)]
         out = []
-        for t0 in range(0, T, Tb):
-            t1 = min(T, t0 + Tb)
-            if t1 <= T0:
-                block = head[:, t0:t1].contiguous()                          # dereverberated above
-            else:
-                block = Y[:, t0:t1].contiguous()
-                block = dereverb.step_block(block) if dereverb else block
-            aff = estimator.step_block(block)                                # (F, K, Tb), a-priori
-            out.append(torch.stack([bf.step_block(block, aff[:, k], 1.0 - aff[:, k]) * aff[:, k]
-                                    for k, bf in enumerate(beamformers)]))   # (K, F, Tb)
-        S = torch.cat(out, dim=2).transpose(1, 2).contiguous()               # (K, T, F)
+
+        def separate(block):                                                 # (F, m, D), dereverberated
+            aff = estimator.step_block(block)                                # (F, K, m), a-priori
+            S = torch.stack([bf.step_block(block, aff[:, k], 1.0 - aff[:, k]) * aff[:, k]
+                             for k, bf in enumerate(beamformers)])           # (K, F, m)
+            out.append(synthesis.step_block(S))                              # (K, samples)
+
+        for t0 in range(0, head.shape[1], Tb):
+            separate(head[:, t0:t0 + Tb].contiguous())
+        starts = list(range(n0, x.shape[1], block_samples))
+        for s0 in starts + [None]:                                           # None: the end of the stream
+            frames = analysis.flush() if s0 is None else analysis.step_block(x[:, s0:s0 + block_samples])
+            if frames.shape[1]:
+                separate(dereverb.step_block(frames) if dereverb else frames)
+        out.append(synthesis.flush())
+        y = torch.cat(out, dim=-1)[..., :n]                                  # (K, samples)
         flagged = int((estimator.status != 0).sum())
-        mark(f'{len(out)} blocks of {Tb}: '
-             f'{"OnlineWPE + " if dereverb else ""}OnlineCACGMM + {K} OnlineMVDR'
+        latency = analysis.window_length - args.shift + block_samples
+        mark(f'{len(starts)} blocks of {block_samples} samples: OnlineSTFT + '
+             f'{"OnlineWPE + " if dereverb else ""}OnlineCACGMM + {K} OnlineMVDR + OnlineISTFT'
              f'{f" ({flagged} bins flagged)" if flagged else ""}')
-        y = istft(S, args.size, args.shift)[..., :n]                         # (K, samples)
-        mark('istft')
+        notes[:] = [f'algorithmic latency: {latency} samples = {latency / args.rate * 1e3:.1f} ms '
+                    f'(window_length - shift = {analysis.window_length - args.shift} + the block '
+                    f'of {block_samples})']
         return y, marks
 
     if args.online:
@@ -192,11 +211,15 @@ def main():
     torch.cuda.synchronize()
     y, marks = run(x)
     est = y.cpu().numpy()
+    if args.save:
+        np.save(args.save, est)
     total = marks[-1][1] - marks[0][1]
     print(f'{args.sensors} sensors x {args.seconds:g} s @ {args.rate} Hz, {K} classes: '
           f'{total * 1e3:.2f} ms on the device = {args.seconds / total:.0f} x real time')
     for (_, a), (name, b) in zip(marks[:-1], marks[1:]):
         print(f'  {name:32s} {(b - a) * 1e3:8.3f} ms')
+    for note in notes:
+        print(f'  {note}')
 
     def corr(a, b):
         return abs(np.dot(a, b)) / (np.linalg.norm(a) * np.linalg.norm(b) + 1e-30)

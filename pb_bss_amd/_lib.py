@@ -276,6 +276,15 @@ SIGNATURES = {
         vp, vp, vp, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES)
+# include/pbbss_stream.h, the section of the ABI whose state lives in tensors of the caller: the
+# handle only names the device, nothing of its memory is used (tests/test_stream_symbols.py);
+# reached through launch_stream below
+STREAM_SIGNATURES = {
+    'pbbss_stft_stream': [vp, vp, i32, i64, i64, vp, vp, i64, i64, i32, i32, i32, i32, i32, vp,
+        i32, i32, i32, vp, vp],
+    'pbbss_istft_stream': [vp, vp, i32, i64, i32, i64, i64, i64, i32, i32, i32, vp, vp, i32, vp,
+        i64, vp],
+}
 
 
 class PbbssError(RuntimeError):
@@ -303,7 +312,7 @@ def load():
         # runtimes and whichever initialises second reports "no ROCm-capable device".
         import torch  # noqa: F401
         lib = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_char_p if name == 'pbbss_error_string' else ctypes.c_int
@@ -404,7 +413,8 @@ def _ref(a):
 _CONVERTERS = {
     name: tuple(ptr if c is vp else float if c is dbl else int if c in (i32, u32, i64) else _ref
                 for c in argtypes[1:])
-    for name, argtypes in SIGNATURES.items() if argtypes and argtypes[0] is vp}
+    for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES}.items()
+    if argtypes and argtypes[0] is vp}
 
 
 def _index(device):
@@ -446,10 +456,10 @@ def _ordered_stream(index):
 def launch(name, device, *args, what=None, accept=()):
     """Call an export whose first parameter is the handle and whose last is the stream: this
     thread's handle of `device` (a torch.device or an index), `args` marshalled slot by slot from
-    SIGNATURES[name] (pointer slots: None, a contiguous device tensor or a ctypes object; option
-    structs by reference; scalars through int() / float()), the current torch stream of the device
-    read now and ordered behind the stream of the handle's previous launch.  Raises through
-    check(rc, what or name) unless rc is in `accept`; returns rc."""
+    SIGNATURES[name] or STREAM_SIGNATURES[name] (pointer slots: None, a contiguous device tensor or
+    a ctypes object; option structs by reference; scalars through int() / float()), the current
+    torch stream of the device read now and ordered behind the stream of the handle's previous
+    launch.  Raises through check(rc, what or name) unless rc is in `accept`; returns rc."""
     index = _index(device)
     converters = _CONVERTERS[name]
     argv = _marshal(name, converters, len(converters) - 1, args)
@@ -458,6 +468,17 @@ def launch(name, device, *args, what=None, accept=()):
     if rc != OK and rc not in accept:
         check(rc, what or name)
     return rc
+
+
+def launch_stream(entry, device, *args, **kw):
+    """`launch` for the second table: STREAM_SIGNATURES['pbbss_<entry>_stream'] ('stft', 'istft'),
+    the exports of include/pbbss_stream.h.  They take the handle and the stream like every launch
+    but no memory of the handle; the ordering of `launch` behind the handle's previous stream is
+    kept all the same, since their inputs usually come from calls that do."""
+    name = f'pbbss_{entry}_stream'
+    if name not in STREAM_SIGNATURES:
+        raise KeyError(f'{name} is no export of include/pbbss_stream.h')
+    return launch(name, device, *args, **kw)
 
 
 def control(name, device_index, *args, what=None):

@@ -1531,6 +1531,44 @@ def istft(X, size, shift, synthesis_window, *, fading=True):
     return out
 
 
+def stft_stream(x, n, hist_in, hist_out, samples_seen, frames_seen, m, size, shift, window, *,
+                fading=True, flush=False, layout=0, out_c128=True):
+    """pbbss_stft_stream.  x (C, n) float32/float64 (None for n = 0), hist_in / hist_out (C, H)
+    float64, H = max(1, window_length - 1), two different buffers; the counters are host integers.
+
+    Writes the history behind the block into hist_out and returns the m frames as (C, m, F)
+    [layout 0] or (F, m, C) [layout 1]."""
+    t = _t()
+    C = hist_in.shape[0]
+    wl = int(window.shape[0])
+    F = size // 2 + 1
+    shape = (C, m, F) if layout == 0 else (F, m, C)
+    out = t.empty(shape, dtype=t.complex128 if out_c128 else t.complex64, device=hist_in.device)
+    _lib.launch_stream('stft', hist_in.device, x, x is not None and x.dtype == t.float64, C, n,
+                       hist_in, hist_out, samples_seen, frames_seen, m, bool(flush), size, shift,
+                       wl, window, bool(fading), layout, bool(out_c128), out if m else None,
+                       what=f'stft_stream(C={C},n={n},m={m},size={size},shift={shift},'
+                            f'window_length={wl})')
+    return out
+
+
+def istft_stream(X, size, shift, synthesis_window, tail, skip):
+    """pbbss_istft_stream.  X (rows, m, F) complex64/complex128, any strides; tail
+    (rows, window_length - shift) float64 contiguous, updated in place ->
+    (rows, m * shift - skip) float64."""
+    t = _t()
+    rows, m, F = X.shape
+    wl = int(synthesis_window.shape[0])
+    n_out = max(0, m * shift - skip)
+    out = t.empty((rows, n_out), dtype=t.float64, device=X.device)
+    _lib.launch_stream('istft', X.device, _lib.view_ptr(X), X.dtype == t.complex128, rows, m,
+                       X.stride(0), X.stride(1), X.stride(2), size, shift, wl, synthesis_window,
+                       tail, skip, out if n_out else None, n_out,
+                       what=f'istft_stream(rows={rows},m={m},size={size},shift={shift},'
+                            f'window_length={wl})')
+    return out
+
+
 def griffin_lim(X, y, x_hat, size, shift, analysis_window, synthesis_window, *, fading=False,
                 iterations=1):
     """pbbss_griffin_lim.  X (B,K,T,F) complex64/complex128, y (B,n) float64 (MISI) or None
