@@ -3,23 +3,14 @@
 // kept by a rank-one (Sherman-Morrison) update, the Souden vector and its output per frame.
 //
 // One wavefront per problem, persistent over the frames of the call, and no workgroup barrier:
-// the four wavefronts of a workgroup never meet.  Both D x D matrices live in registers as FULL
-// matrices on a lane grid -- lane l owns row l / LPR and the columns l % LPR + k LPR, k < E, with
-// (LPR, E) = (4, 1), (8, 1), (4, 4) for the sensor bounds 4, 8, 16 -- but every lane computes the
-// element of the LOWER triangle that it owns or mirrors, (max(r, c), min(r, c)), with the same
-// instructions on the same values as its mirror lane, and stores the conjugate when it sits above
-// the diagonal.  The upper triangle therefore is the conjugate mirror to the bit, as the definition
-// demands, and no transpose ever crosses the lanes.  Rows and columns beyond D hold zeros, which
-// every update maps to zeros.
+// the four wavefronts of a workgroup never meet.  Phi and Psi live in registers on the lane grid
+// of lane_grid.hpp, Hermitian to the bit.
 //
-// Frames and masks are staged a tile ahead in registers and handed to the wavefront's own slice of
-// LDS at the tile's start, so no global load sits on the frame chain; a frame's y_r, y_c and masks
-// are read from LDS one frame ahead of their use.  Per frame:
+// Frames and masks are staged a tile ahead (frame_tile.hpp); a frame's y_r, y_c and masks are read
+// from LDS one frame ahead of their use.  Per frame:
 //   Phi <- alpha Phi + s y y^H
-//   n = Psi y: E products per lane, row sums by DPP (quad permutes, half-row mirror) -- a fixed
-//       tree, so the order of the additions never depends on blocking or on the batch;
+//   n = Psi y: E products per lane, row sums by DPP;
 //   den = alpha + v Re(y^H n): the 64-lane DPP / permlane-swap tree over Re(conj(y_r) p_lane);
-//   n_c from the lanes of row c (the one LDS-crossbar hop on the chain Psi -> Psi);
 //   Psi <- (Psi - (v / den) n n^H) / alpha
 //   u = Phi[:, ref] as conj(Phi[ref, c]) from the lanes of row ref; q = Psi u by row sums;
 //   lam = sum Re(Psi_ij conj(Phi_ij)) on the 64-lane tree; w = q / max(lam, tiny); x = w^H y on
@@ -31,7 +22,8 @@
 #include <float.h>
 #include <math.h>
 #include "dispatch.hpp"
-#include "pbbss_dev.hpp"
+#include "frame_tile.hpp"
+#include "lane_grid.hpp"
 
 namespace pbbss {
 namespace {
@@ -39,44 +31,6 @@ namespace {
 constexpr int kTile = kOnlineBfTile;
 constexpr int kWaves = kOnlineBfWaves;
 static_assert(kTile == 32, "one lane per frame and mask: lanes 0..31 target, 32..63 noise");
-
-__device__ __forceinline__ double2 load_frame(const WpeFrames& y, int64_t i) {
-  if (y.c128) return static_cast<const double2*>(y.p)[i];
-  const float2 v = static_cast<const float2*>(y.p)[i];
-  return make_double2((double)v.x, (double)v.y);
-}
-
-// element idx of a tile of nf frames -> (sensor, frame); the inner index is the axis that is
-// contiguous in memory
-struct TileAt {
-  int d, u;
-};
-__device__ __forceinline__ TileAt tile_index(const WpeFrames& y, int idx, int nf) {
-  const bool sensors_inner = y.sd == 1 && y.D > 1;
-  const int q = idx / (sensors_inner ? y.D : nf), m = idx - q * (sensors_inner ? y.D : nf);
-  return sensors_inner ? TileAt{m, q} : TileAt{q, m};
-}
-
-// The lanes of a wavefront read LDS that other lanes of the same wavefront wrote: the hardware
-// keeps a wavefront's LDS operations in order, this keeps the compiler from reordering them.
-__device__ __forceinline__ void wave_lds_order() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// sum over the LPR lanes of a row of the lane grid, on every lane of the row
-template <int LPR>
-__device__ __forceinline__ void row_sum(double& a, double& b) {
-  a += dpp_mov_f64<kDppQuadXor1>(a);
-  b += dpp_mov_f64<kDppQuadXor1>(b);
-  a += dpp_mov_f64<kDppQuadXor2>(a);
-  b += dpp_mov_f64<kDppQuadXor2>(b);
-  if constexpr (LPR == 8) {
-    a += dpp_mov_f64<kDppRowHalfMirror>(a);
-    b += dpp_mov_f64<kDppRowHalfMirror>(b);
-  }
-}
 
 template <int E>
 struct FrameIn {
@@ -87,10 +41,8 @@ struct FrameIn {
 template <int DB>
 __global__ __launch_bounds__(kWaves * kWave) void online_mvdr_kernel(WpeFrames y, OnlineBfArgs a,
                                                                      int64_t B) {
-  constexpr int LPR = DB == 8 ? 8 : 4;  // lanes per row of the lane grid
-  constexpr int E = DB / LPR;           // columns per lane
-  constexpr int kPre = kTile * DB / kWave;  // elements of a tile per lane
-  static_assert(LPR * DB <= kWave && E * LPR == DB && kPre * kWave == kTile * DB);
+  using Grid = LaneGrid<DB>;
+  constexpr int LPR = Grid::LPR, E = Grid::E;
   __shared__ double2 fr_s[kWaves][kTile * DB];  // [frame][sensor], zeros beyond D
   __shared__ double2 xo_s[kWaves][kTile];
   __shared__ double mk_s[kWaves][2 * kTile];    // target masks | noise masks
@@ -100,52 +52,29 @@ __global__ __launch_bounds__(kWaves * kWave) void online_mvdr_kernel(WpeFrames y
   double2* fr = fr_s[wave];
   double2* xo = xo_s[wave];
   double* mk = mk_s[wave];
-  const int D = y.D, r = lane / LPR, cl = lane - r * LPR;
-  const bool rowok = r < D, head = rowok && cl == 0;
-  const int rr = rowok ? r : 0;
+  const int D = y.D;
+  const Grid g(lane, D);
+  const bool head = g.rowok && g.cl == 0;
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   const double alpha = a.alpha, inv_alpha = 1.0 / a.alpha;
 
-  // ---- the state: the lower triangle and the real diagonal are read
+  // ---- the state
   double2 phi[E], psi[E];
-  bool lower[E], diag[E], act[E];
-  const double2* Phi = reinterpret_cast<const double2*>(a.target_psd) + b * D * D;
-  const double2* Psi = reinterpret_cast<const double2*>(a.noise_inv) + b * D * D;
-#pragma unroll
-  for (int k = 0; k < E; ++k) {
-    const int c = cl + k * LPR;
-    act[k] = rowok && c < D;
-    lower[k] = r >= c;
-    diag[k] = r == c;
-    phi[k] = psi[k] = make_double2(0.0, 0.0);
-    if (act[k]) {
-      const int at = lower[k] ? r * D + c : c * D + r;
-      phi[k] = Phi[at];
-      psi[k] = Psi[at];
-      if (!lower[k]) phi[k].y = -phi[k].y, psi[k].y = -psi[k].y;
-      if (diag[k]) phi[k].y = psi[k].y = 0.0;
-    }
-  }
+  double2* Phi = reinterpret_cast<double2*>(a.target_psd) + b * D * D;
+  double2* Psi = reinterpret_cast<double2*>(a.noise_inv) + b * D * D;
+  g.load_hermitian(Phi, D, phi);
+  g.load_hermitian(Psi, D, psi);
   for (int i = lane; i < kTile * DB; i += kWave) fr[i] = make_double2(0.0, 0.0);
   const int64_t seen = a.frames_seen[b];
   bool dead = false;
 
-  double2 pre[kPre];
+  TilePrefetch<kTile, DB, kWave> pre;
   double mpre = 0.0;
   auto fetch = [&](int64_t t0) {
-    const int nf = (int)(T - t0 < kTile ? T - t0 : kTile);
-#pragma unroll
-    for (int i = 0; i < kPre; ++i) {
-      const int idx = lane + kWave * i;
-      pre[i] = make_double2(0.0, 0.0);
-      if (idx < nf * D) {
-        const TileAt at = tile_index(y, idx, nf);
-        pre[i] = load_frame(y, b * y.sb + at.d * y.sd + (t0 + at.u) * y.st);
-      }
-    }
+    pre.fetch(y, b, t0, lane);
     const int u = lane & (kTile - 1);
     mpre = 0.0;
-    if (u < nf) {
+    if (u < pre.frames(T, t0)) {
       const void* m = lane < kTile ? a.target_mask : a.noise_mask;
       const int64_t at = b * T + t0 + u;
       mpre = a.mask_f64 ? static_cast<const double*>(m)[at]
@@ -154,10 +83,7 @@ __global__ __launch_bounds__(kWaves * kWave) void online_mvdr_kernel(WpeFrames y
   };
   auto read = [&](int u) {
     FrameIn<E> f;
-    const double2 v = fr[u * DB + rr];
-    f.yr = rowok ? v : make_double2(0.0, 0.0);
-#pragma unroll
-    for (int k = 0; k < E; ++k) f.yc[k] = fr[u * DB + cl + k * LPR];
+    g.read_frame(fr, u, f.yr, f.yc);
     f.s = mk[u];
     f.v = mk[kTile + u];
     return f;
@@ -165,15 +91,8 @@ __global__ __launch_bounds__(kWaves * kWave) void online_mvdr_kernel(WpeFrames y
   fetch(0);
 
   for (int64_t t0 = 0; t0 < T; t0 += kTile) {
-    const int nf = (int)(T - t0 < kTile ? T - t0 : kTile);
-#pragma unroll
-    for (int i = 0; i < kPre; ++i) {
-      const int idx = lane + kWave * i;
-      if (idx < nf * D) {
-        const TileAt at = tile_index(y, idx, nf);
-        fr[at.u * DB + at.d] = pre[i];
-      }
-    }
+    const int nf = pre.frames(T, t0);
+    pre.stage(y, t0, lane, fr, [](int u, int d) { return u * DB + d; });
     mk[lane] = mpre;
     wave_lds_order();
     if (t0 + kTile < T) fetch(t0 + kTile);  // in flight during the frames of this tile
@@ -182,7 +101,7 @@ __global__ __launch_bounds__(kWaves * kWave) void online_mvdr_kernel(WpeFrames y
     for (int u = 0; u < nf; ++u) {
       const FrameIn<E> f = nxt;
       nxt = read(u + 1 < kTile ? u + 1 : u);  // a frame ahead of its use
-      double2* wo = a.out_w ? reinterpret_cast<double2*>(a.out_w) + ((t0 + u) * B + b) * D + r
+      double2* wo = a.out_w ? reinterpret_cast<double2*>(a.out_w) + ((t0 + u) * B + b) * D + g.r
                             : nullptr;
       if (dead) {
         if (lane == 0) xo[u] = make_double2(nan, nan);
@@ -192,12 +111,12 @@ __global__ __launch_bounds__(kWaves * kWave) void online_mvdr_kernel(WpeFrames y
       // ---- Phi <- alpha Phi + s y y^H, the element (max(r, c), min(r, c)) on either lane
 #pragma unroll
       for (int k = 0; k < E; ++k) {
-        const double2 p = lower[k] ? f.yr : f.yc[k], q = lower[k] ? f.yc[k] : f.yr;
+        const double2 p = g.lower[k] ? f.yr : f.yc[k], q = g.lower[k] ? f.yc[k] : f.yr;
         const double re = p.x * q.x + p.y * q.y, im = p.y * q.x - p.x * q.y;
-        double ly = lower[k] ? phi[k].y : -phi[k].y;
+        double ly = g.lower[k] ? phi[k].y : -phi[k].y;
         phi[k].x = alpha * phi[k].x + f.s * re;
-        ly = diag[k] ? 0.0 : alpha * ly + f.s * im;
-        phi[k].y = lower[k] ? ly : -ly;
+        ly = g.diag[k] ? 0.0 : alpha * ly + f.s * im;
+        phi[k].y = g.lower[k] ? ly : -ly;
       }
       // ---- n = Psi y and den = alpha + v Re(y^H n)
       double nr = 0.0, ni = 0.0;
@@ -207,38 +126,26 @@ __global__ __launch_bounds__(kWaves * kWave) void online_mvdr_kernel(WpeFrames y
         ni += psi[k].x * f.yc[k].y + psi[k].y * f.yc[k].x;
       }
       const double den = alpha + f.v * wave_sum(f.yr.x * nr + f.yr.y * ni);
-      row_sum<LPR>(nr, ni);
+      row_sums<LPR, 1>(&nr, &ni);
       if (!(den > 0.0) || !isfinite(den)) {  // the same value in every lane
         dead = true;  // from this frame on
         if (lane == 0) xo[u] = make_double2(nan, nan);
         if (wo && head) *wo = make_double2(nan, nan);
         continue;
       }
-      const double g = f.v / den;
-      // ---- Psi <- (Psi - g n n^H) / alpha
-#pragma unroll
-      for (int k = 0; k < E; ++k) {
-        const int src = (cl + k * LPR) * LPR;  // a lane of row c
-        const double cr = lane_get(nr, src), ci = lane_get(ni, src);
-        const double Rr = lower[k] ? nr : cr, Ri = lower[k] ? ni : ci;
-        const double Cr = lower[k] ? cr : nr, Ci = lower[k] ? ci : ni;
-        const double kx = Rr * g, ky = Ri * g;
-        double ly = lower[k] ? psi[k].y : -psi[k].y;
-        psi[k].x = (psi[k].x - (kx * Cr + ky * Ci)) * inv_alpha;
-        ly = diag[k] ? 0.0 : (ly - (ky * Cr - kx * Ci)) * inv_alpha;
-        psi[k].y = lower[k] ? ly : -ly;
-      }
+      // ---- Psi <- (Psi - (v / den) n n^H) / alpha
+      g.downdate(psi, nr, ni, f.v / den, inv_alpha);
       // ---- the Souden vector of the statistics that include this frame
       double qr = 0.0, qi = 0.0, lam = 0.0;
 #pragma unroll
       for (int k = 0; k < E; ++k) {
-        const int src = a.ref * LPR + cl;  // Phi[ref, c]: its conjugate is u_c = Phi[c, ref]
+        const int src = a.ref * LPR + g.cl;  // Phi[ref, c]: its conjugate is u_c = Phi[c, ref]
         const double ur = lane_get(phi[k].x, src), ui = -lane_get(phi[k].y, src);
         qr += psi[k].x * ur - psi[k].y * ui;
         qi += psi[k].x * ui + psi[k].y * ur;
         lam += psi[k].x * phi[k].x + psi[k].y * phi[k].y;
       }
-      row_sum<LPR>(qr, qi);
+      row_sums<LPR, 1>(&qr, &qi);
       lam = wave_sum(lam);
       const double rl = 1.0 / fmax(lam, DBL_MIN);
       double2 w = make_double2(qr * rl, qi * rl);
@@ -267,17 +174,8 @@ __global__ __launch_bounds__(kWaves * kWave) void online_mvdr_kernel(WpeFrames y
     wave_lds_order();
   }
 
-  // ---- the state: the whole matrices, Hermitian to the bit
-  double2* PhiO = reinterpret_cast<double2*>(a.target_psd) + b * D * D;
-  double2* PsiO = reinterpret_cast<double2*>(a.noise_inv) + b * D * D;
-#pragma unroll
-  for (int k = 0; k < E; ++k) {
-    if (act[k]) {
-      const int at = r * D + cl + k * LPR;
-      PhiO[at] = dead ? make_double2(nan, nan) : phi[k];
-      PsiO[at] = dead ? make_double2(nan, nan) : psi[k];
-    }
-  }
+  g.store_hermitian(Phi, D, phi, dead);
+  g.store_hermitian(Psi, D, psi, dead);
   if (lane == 0) {
     a.frames_seen[b] = seen + T;
     a.status[b] = dead ? (int32_t)PBBSS_ST_NONFINITE : 0;

@@ -28,6 +28,7 @@
 #include "wpe.hpp"
 #include <math.h>
 #include "dispatch.hpp"
+#include "frame_tile.hpp"
 #include "launch_util.hpp"
 
 namespace pbbss {
@@ -35,12 +36,6 @@ namespace {
 
 constexpr int kThreads = 256;
 typedef double double4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double2 load_frame(const WpeFrames& y, int64_t i) {
-  if (y.c128) return static_cast<const double2*>(y.p)[i];
-  const float2 v = static_cast<const float2*>(y.p)[i];
-  return make_double2((double)v.x, (double)v.y);
-}
 
 // frames f0 .. f0 + W - 1 of every sensor of problem b to dst[d * WS + u]; frames outside the row
 // are zeros.  The inner index of the copy is the axis that is contiguous in memory.

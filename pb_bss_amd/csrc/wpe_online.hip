@@ -25,6 +25,7 @@
 // the call.
 #include "wpe_online.hpp"
 #include <math.h>
+#include "frame_tile.hpp"
 #include "launch_util.hpp"
 
 namespace pbbss {
@@ -32,25 +33,8 @@ namespace {
 
 constexpr int kTile = kWpeOnlineTile;
 
-__device__ __forceinline__ double2 load_frame(const WpeFrames& y, int64_t i) {
-  if (y.c128) return static_cast<const double2*>(y.p)[i];
-  const float2 v = static_cast<const float2*>(y.p)[i];
-  return make_double2((double)v.x, (double)v.y);
-}
-
-// element idx of a tile of nf frames -> (sensor, frame); the inner index is the axis that is
-// contiguous in memory
-__device__ __forceinline__ void tile_index(const WpeFrames& y, int idx, int nf, int& d, int& u) {
-  if (y.sd == 1 && y.D > 1) {
-    u = idx / y.D;
-    d = idx - u * y.D;
-  } else {
-    d = idx / nf;
-    u = idx - d * nf;
-  }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
+// a __shfl_xor butterfly, not the DPP tree of pbbss_dev.hpp's wave_sum: it adds in another order
+__device__ __forceinline__ double wave_sum_xor(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -70,7 +54,6 @@ constexpr int NT = kWpeOnlineThreads;
 
 __global__ __launch_bounds__(NT) void wpe_online_kernel(WpeFrames y, OnlineArgs a) {
   extern __shared__ double2 wpe_online_lds[];
-  constexpr int kPre = kTile * kWpeMaxD / NT;  // elements of a tile per thread
   const int tid = threadIdx.x, lane = tid & 63;
   const int D = y.D, M = D * a.taps, Me = M + D, H = a.taps + a.delay;
   const int tri = M * (M + 1) / 2;
@@ -116,35 +99,14 @@ __global__ __launch_bounds__(NT) void wpe_online_kernel(WpeFrames y, OnlineArgs 
   bool dead = false;
   int bad = 0;
 
-  double2 pre[kPre];
-  auto fetch = [&](int64_t t0) {
-    const int nf = (int)(T - t0 < kTile ? T - t0 : kTile);
-#pragma unroll
-    for (int i = 0; i < kPre; ++i) {
-      const int idx = tid + NT * i;
-      pre[i] = make_double2(0.0, 0.0);
-      if (idx < nf * D) {
-        int d, u;
-        tile_index(y, idx, nf, d, u);
-        pre[i] = load_frame(y, b * y.sb + d * y.sd + (t0 + u) * y.st);
-      }
-    }
-  };
-  fetch(0);
+  TilePrefetch<kTile, kWpeMaxD, NT> pre;
+  pre.fetch(y, b, 0, tid);
 
   for (int64_t t0 = 0; t0 < T; t0 += kTile) {
-    const int nf = (int)(T - t0 < kTile ? T - t0 : kTile);
-#pragma unroll
-    for (int i = 0; i < kPre; ++i) {
-      const int idx = tid + NT * i;
-      if (idx < nf * D) {
-        int d, u;
-        tile_index(y, idx, nf, d, u);
-        fr[(kTile - 1 - u) * D + d] = pre[i];
-      }
-    }
+    const int nf = pre.frames(T, t0);
+    pre.stage(y, t0, tid, fr, [D](int u, int d) { return (kTile - 1 - u) * D + d; });
     __syncthreads();
-    if (t0 + kTile < T) fetch(t0 + kTile);  // in flight during the frames of this tile
+    if (t0 + kTile < T) pre.fetch(y, b, t0 + kTile, tid);  // in flight during this tile's frames
     if (tid < nf) {
       const int u = tid;
       if (a.power) {
@@ -229,8 +191,8 @@ __global__ __launch_bounds__(NT) void wpe_online_kernel(WpeFrames y, OnlineArgs 
         const double2 x = xs[lane];
         chk = isfinite(x.x) && isfinite(x.y) ? 0.0 : 1.0;
       }
-      t = wave_sum(t);
-      chk = wave_sum(chk);
+      t = wave_sum_xor(t);
+      chk = wave_sum_xor(chk);
       const double den = a.alpha * lam[u] + t;
       if (!isfinite(den) || chk != 0.0) {  // the same value in every thread
         dead = true;  // from this frame on
@@ -275,10 +237,9 @@ __global__ __launch_bounds__(NT) void wpe_online_kernel(WpeFrames y, OnlineArgs 
     __syncthreads();
     // ---- the tile of x, with the strides and the type of y
     for (int idx = tid; idx < nf * D; idx += NT) {
-      int d, u;
-      tile_index(y, idx, nf, d, u);
-      const double2 x = xo[u * D + d];
-      const int64_t i = b * y.sb + d * y.sd + (t0 + u) * y.st;
+      const TileAt at = tile_index(y, idx, nf);
+      const double2 x = xo[at.u * D + at.d];
+      const int64_t i = b * y.sb + at.d * y.sd + (t0 + at.u) * y.st;
       if (y.c128)
         static_cast<double2*>(a.out_x)[i] = x;
       else
